@@ -2,21 +2,36 @@
 """Benchmark: device-resident EncHead+MD5 encode then decode+verify+compact (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--tag md5|table]
-                  [--no-cpu-baseline] [--eager]
+                  [--full] [--dump-outputs DIR] [--no-cpu-baseline] [--eager]
 
 One step = one pass of the hot path over one batch: k_encode (RConn::Output framing of every
 packet) followed by k_decode + k_compact (RConn::OnRecv of every frame), inputs resident in HBM.
 The headline computes the tag by one MD5 compression per packet and lane in both kernels
-(RSK_TAG_MD5, as util/rhash.cpp:20-41 does per packet); at N = 1 the same step with the tag looked
-up in the key's 256-entry table (RSK_TAG_TABLE) is timed afterwards and reported under its own
-label (`variant_tag_table_lut`), never as `value`.
+(RSK_TAG_MD5, as util/rhash.cpp:20-41 does per packet).
 The timed region replays a HIP graph of the step (one host launch per step; --eager: the three
-library calls per step instead); the per-kernel times behind `roofline` come from HIP events on
-the step's stream around the same launches issued one by one right after the timed region.
+library calls per step instead).
+
+A plain run does only what the headline needs: it builds the workload, warms up, times the K steps,
+writes the outputs if --dump-outputs is given and prints the result line (metric, value, unit,
+ms_per_step, config, gib_per_s, encode_path).  Everything else is behind --full:
+  * the per-kernel times (`kernels_ms`) and the `roofline` of a graph-mode run: HIP events on the
+    step's stream around the same launches issued one by one right after the timed region (K more
+    steps; an --eager run records the events inside its timed region and reports them either way)
+  * at N = 1 the same step with the tag looked up in the key's 256-entry table (RSK_TAG_TABLE),
+    timed after the headline and reported under its own label (`variant_tag_table_lut`), never as
+    `value` (--no-tag-variant skips it)
+  * at N = 1 the scaling curve's N = 1 point, `scale_n1_c5` (below; --no-scale-anchor skips it)
+  * at N = 1 the CPU baseline (`cpu_baseline`; --no-cpu-baseline skips it)
+
+--dump-outputs DIR writes what the last timed step left in the step's output buffers, as
+DIR/<name>.npy in float32 / float64 (rank r > 0: DIR/<name>.rank<r>.npy): the encoder's status and
+frame slots and every field of the decoder's SoA output, for a fixed, seeded sample of the packets
+(dump_outputs below lists the files).  The workload is generated from fixed seeds, so two builds
+run with the same arguments write arrays that can be compared element for element.
 
 Workload: N = 1 defaults to C3 (4M x 1400-B packets, the metric's target config); N > 1 defaults
 to C5 (BASELINE configs[4]: 64M x 1400-B packets in total, contiguous shards, strong scaling), so
-`--gpus 8` IS config 5.  The scaling curve's N = 1 point is the `scale_n1_c5` key of the default
+`--gpus 8` IS config 5.  The scaling curve's N = 1 point is the `scale_n1_c5` key of the `--full`
 N = 1 line: after the C3 headline (and its tag variant) the C3 arenas are freed and C5 is timed whole
 on the same GPU with the same step (`--gpus 1 --config c5` makes it the headline instead).  A
 1/2/4/8 curve therefore reads scale_n1_c5.value at N = 1 and value at N = 2, 4, 8.
@@ -245,9 +260,10 @@ def make_runner(torch, dist, workload, d, w, cx, stream, graph_mode: bool):
 
     captured_path = [None]
 
-    def timed(mode: str, steps: int, warmup: int, sync_ranks: bool):
+    def timed(mode: str, steps: int, warmup: int, sync_ranks: bool, per_kernel: bool = True, after=None):
         """Warm up, capture the step as a graph (the tag mode is fixed at capture), time `steps`
-        replays between barriers, then per-kernel HIP events on the step's stream."""
+        replays between barriers, call `after()` on the last timed step's outputs, then (per_kernel)
+        per-kernel HIP events on the step's stream.  Returns (elapsed, events or None)."""
         cx.set_tag_mode(mode)
         with torch.cuda.stream(stream):
             for _ in range(warmup):
@@ -269,7 +285,9 @@ def make_runner(torch, dist, workload, d, w, cx, stream, graph_mode: bool):
             for _ in range(warmup):  # the warmup steps again, as replays of the graph
                 graph.replay()
             torch.cuda.synchronize()
-        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(steps)]
+        evs = None
+        if graph is None or per_kernel:
+            evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(steps)]
         if sync_ranks:
             dist.barrier()
         torch.cuda.synchronize()
@@ -285,7 +303,9 @@ def make_runner(torch, dist, workload, d, w, cx, stream, graph_mode: bool):
         el = time.perf_counter() - t0
         gate("timed region")
         cx.check_device_errors()  # raises if a compaction look-back gave up (rsk_check_device_errors)
-        if graph is not None:
+        if after is not None:
+            after()
+        if graph is not None and per_kernel:
             # per-kernel durations for the roofline: HIP events on the step's stream around the same
             # launches, issued one by one (the graph replays the identical kernels and arguments)
             with torch.cuda.stream(stream):
@@ -296,6 +316,71 @@ def make_runner(torch, dist, workload, d, w, cx, stream, graph_mode: bool):
         return el, evs
 
     return timed, captured_path
+
+
+DUMP_PACKETS = 1 << 17  # packets whose per-packet outputs are dumped
+DUMP_FRAMES = 4096  # packets whose whole frame slot is dumped
+
+
+def dump_sample(n: int, k: int, seed: int) -> np.ndarray:
+    """min(n, k) distinct packet indices of [0, n), ascending: every packet when n <= k, else a draw
+    without replacement from a fixed seed (the same for every run and build)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False, shuffle=False).astype(np.int64))
+
+
+def dump_outputs(torch, dirpath: str, d, w, rank: int = 0) -> dict:
+    """--dump-outputs: what the step's caller holds after the last timed step, for a fixed sample of
+    this shard's packets (about 40 MB at the default shapes), as float32 / float64 .npy files:
+
+      packet_idx            the sampled packets (shard-local indices, ascending)
+      enc_status            output_batch's status of each (the frame length, or <= 0: not sent)
+      dec_<field>           onrecv_batch's SoA output of each: status, hlen, cmd, id (8 bytes per
+                            packet), conv, conn_key (u64 as [low, high] 32-bit halves), pay_off, pay_len
+      dec_n_valid           the compaction's count
+      dec_valid_idx         VALID list entries at positions packet_idx (-1 at positions >= n_valid)
+      frame_idx, frames     a smaller sample of packets and the whole frame slot of each (one row of
+                            frame_pitch bytes per packet: the frame and its zero pad)
+
+    Returns {name: shape}."""
+    os.makedirs(dirpath, exist_ok=True)
+    dev = w.frame.device
+    idx = dump_sample(d.n, DUMP_PACKETS, 0x5EED0001)
+    fidx = dump_sample(d.n, DUMP_FRAMES, 0x5EED0002)
+    t_idx = torch.from_numpy(idx).to(dev)
+    t_fidx = torch.from_numpy(fidx).to(dev)
+
+    def take(t, cols=1):
+        a = t.view(-1, cols)[t_idx] if cols > 1 else t[t_idx]
+        return a.cpu().numpy()
+
+    dec = w.dec
+    nv = int(dec.n_valid.item())
+    conn_key = take(dec.conn_key).view(np.uint64)
+    valid_idx = take(dec.valid_idx).view(np.uint32).astype(np.float64)
+    valid_idx[idx >= nv] = -1.0
+    out = {
+        "packet_idx": idx.astype(np.float64),
+        "enc_status": take(w.status).astype(np.float64),
+        "dec_status": take(dec.status).astype(np.float32),
+        "dec_hlen": take(dec.hlen).astype(np.float32),
+        "dec_cmd": take(dec.cmd).astype(np.float32),
+        "dec_id": take(dec.id, 8).astype(np.float32),
+        "dec_conv": take(dec.conv).view(np.uint32).astype(np.float64),
+        "dec_conn_key": np.stack([conn_key & np.uint64(0xFFFFFFFF), conn_key >> np.uint64(32)],
+                                 axis=1).astype(np.float64),
+        "dec_pay_off": take(dec.pay_off).view(np.uint16).astype(np.float32),
+        "dec_pay_len": take(dec.pay_len).view(np.uint16).astype(np.float32),
+        "dec_n_valid": np.array([nv], np.float64),
+        "dec_valid_idx": valid_idx,
+        "frame_idx": fidx.astype(np.float64),
+        "frames": w.frame.view(d.n, d.frame_pitch)[t_fidx].cpu().numpy().astype(np.float32),
+    }
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def scale_anchor_c5(torch, dist, rc, workload, dev, gpu, tag: str, steps: int, warmup: int, graph_mode: bool):
@@ -342,6 +427,13 @@ def main() -> None:
                          "Default: c3 at N = 1, c5 at N > 1")
     ap.add_argument("--packets", type=int, default=0,
                     help="packets per GPU (c2-c4) or in total (c5); default: the config's")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what a plain run leaves out: per-kernel times and "
+                         "the roofline of a graph-mode run, and at N = 1 the other tag mode, the C5-on-one-GPU "
+                         "point and the CPU baseline (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (a fixed, seeded sample of the "
+                         "packets) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=1 << 20)
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
@@ -355,15 +447,18 @@ def main() -> None:
     ap.add_argument("--tag", default="md5", choices=["md5", "table"],
                     help="tag mode of the headline (default md5: MD5 per lane; table: the LUT variant)")
     ap.add_argument("--no-tag-variant", action="store_true",
-                    help="skip timing the other tag mode after the headline (N = 1)")
+                    help="with --full: skip timing the other tag mode after the headline (N = 1)")
     ap.add_argument("--cpu-baseline-ref", action="store_true",
                     help="time the reference's own codec (oracle/_ref, build container only) as the CPU "
                          "baseline instead of the clean-room restatement")
     ap.add_argument("--no-scale-anchor", action="store_true",
-                    help="skip the C5-on-one-GPU point (`scale_n1_c5`) timed after the C3 headline at N = 1")
+                    help="with --full: skip the C5-on-one-GPU point (`scale_n1_c5`) timed after the C3 headline "
+                         "at N = 1")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal only: every rank uses GPU 0 (N ranks on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -407,7 +502,13 @@ def main() -> None:
     stream = torch.cuda.Stream(dev) if graph_mode else torch.cuda.current_stream()
     timed, captured_path = make_runner(torch, dist, workload, d, w, cx, stream, graph_mode)
 
-    elapsed, evs = timed(args.tag, args.steps, args.warmup, world > 1)
+    dumped = []
+
+    def dump():
+        dumped.append(dump_outputs(torch, args.dump_outputs, d, w, rank))
+
+    elapsed, evs = timed(args.tag, args.steps, args.warmup, world > 1, per_kernel=args.full,
+                         after=dump if args.dump_outputs else None)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -420,18 +521,20 @@ def main() -> None:
         # the per-kernel events time the eager calls after the timed region: they must be the same path
         raise SystemExit(f"bench: graph captured encode path {run_path}, eager calls took "
                          f"{(cx.last_encode_path, cx.last_copy_k)}")
-    enc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
-    dec_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
+    # per-kernel times: --full, or an eager run (its events sit in the timed region); else None
+    enc_ms = dec_ms = None
+    if evs is not None:
+        enc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
+        dec_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
     total_pkts = (n_total if strong else world * d.n) * args.steps
     mpkts = total_pkts / elapsed_max / 1e6
     p = int(d.pay_len[0]) if workload.CONFIGS[cfg][2] == workload.CONFIGS[cfg][3] else int(d.pay_len.mean())
     # algorithmic bytes of this rank's launch, summed over its packets' actual payload lengths
     enc_bytes = int(enc_bytes_per_pkt(d.pay_len.astype(np.int64)).sum())
     bytes_step = enc_bytes + d.n * dec_bytes_per_pkt()
-    achieved = enc_bytes / (enc_ms * 1e-3) / 1e9
 
     other = None
-    if world == 1 and not args.no_tag_variant:
+    if args.full and world == 1 and not args.no_tag_variant:
         # the other tag mode, reported beside the headline under its own label
         omode = "table" if args.tag == "md5" else "md5"
         el_o, evs_o = timed(omode, args.steps, max(2, args.warmup // 2), False)
@@ -440,7 +543,7 @@ def main() -> None:
         other = (omode, el_o, enc_o, dec_o)
 
     anchor = None
-    if world == 1 and cfg == "c3" and not args.packets and not args.no_scale_anchor:
+    if args.full and world == 1 and cfg == "c3" and not args.packets and not args.no_scale_anchor:
         # free the C3 arenas, then the curve's N = 1 point on the same GPU (C5 whole: 185 of 288 GB)
         cx.close()
         cx = None
@@ -451,7 +554,6 @@ def main() -> None:
                                  min(args.warmup, 3), graph_mode)
 
     if rank == 0:
-        tr = load_traffic(cfg, d.n, d.frame_pitch)
         line = {
             "metric": METRIC,
             "value": round(mpkts, 2),
@@ -479,12 +581,18 @@ def main() -> None:
                 "parallelism": f"shard{world} (no collective)",
             },
             "gib_per_s": round(world * bytes_step * args.steps / elapsed_max / 2**30, 2),
-            "kernels_ms": {"encode": round(enc_ms, 4), "decode+compact": round(dec_ms, 4)},
             "encode_path": enc_path,
-            "launch": ("hipGraph replay of the step (encode, k_decode, k_compact); kernel times: HIP events "
-                       "around the same launches issued one by one after the timed region") if graph_mode else
+            "launch": "hipGraph replay of the step (encode, k_decode, k_compact)" if graph_mode else
                       "eager launches; kernel times: HIP events in the timed region",
-            "roofline": {
+        }
+        if enc_ms is not None:
+            if graph_mode:
+                line["launch"] += ("; kernel times: HIP events around the same launches issued one by one "
+                                   "after the timed region")
+            tr = load_traffic(cfg, d.n, d.frame_pitch)
+            achieved = enc_bytes / (enc_ms * 1e-3) / 1e9
+            line["kernels_ms"] = {"encode": round(enc_ms, 4), "decode+compact": round(dec_ms, 4)}
+            line["roofline"] = {
                 "kernel": enc_path,
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
@@ -493,10 +601,11 @@ def main() -> None:
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": None if tr is None else tr["bytes_per_launch"],
                 "algorithmic_bytes_per_launch": enc_bytes,
-            },
-        }
-        if tr is not None:
-            line["roofline"]["traffic_source"] = tr.get("source", "profiles/traffic.json")
+            }
+            if tr is not None:
+                line["roofline"]["traffic_source"] = tr.get("source", "profiles/traffic.json")
+        if dumped:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped[0]}
         if other is not None:
             omode, el_o, enc_o, dec_o = other
             line[f"variant_{TAG_LABEL[omode]}"] = {
@@ -509,7 +618,7 @@ def main() -> None:
             }
         if anchor is not None:
             line["scale_n1_c5"] = anchor
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, min(args.cpu_sample, d.n), args.cpu_seconds,
                                                 use_ref=args.cpu_baseline_ref)
         print(json.dumps(line), flush=True)

@@ -44,6 +44,19 @@ def test_headline_tag_is_md5_per_lane():
     assert "table" in bench.TAG_TEXT["table"]
 
 
+def test_dump_sample_is_fixed_sorted_and_distinct():
+    # --dump-outputs: the same packets in every run; every packet when the shard is small
+    assert np.array_equal(bench.dump_sample(100, 4096, 1), np.arange(100))
+    a = bench.dump_sample(4 << 20, bench.DUMP_PACKETS, 0x5EED0001)
+    assert np.array_equal(a, bench.dump_sample(4 << 20, bench.DUMP_PACKETS, 0x5EED0001))
+    assert a.dtype == np.int64 and 0 <= a[0] and a[-1] < 4 << 20
+    assert np.all(np.diff(a) > 0) and len(a) == bench.DUMP_PACKETS
+    assert len(bench.dump_sample(64 << 20, bench.DUMP_FRAMES, 0x5EED0002)) == bench.DUMP_FRAMES
+    # the dump stays under 64 MB at the widest slot pitch (C4: 1536 B): float32 frame rows, and per
+    # sampled packet 4 float64 scalars, the [low, high] key pair and 13 float32 values
+    assert bench.DUMP_FRAMES * (1536 * 4 + 8) + bench.DUMP_PACKETS * (6 * 8 + 13 * 4) < 64e6
+
+
 def test_cpu_baseline_port_runs_on_a_small_sample():
     if not os.path.exists(oracle_lib.ORACLE_SO):
         pytest.skip("oracle/liboracle.so not built (make -C oracle)")
