@@ -34,6 +34,8 @@
  *                            by cmd (conn/IAppGroup.cpp:76-96), ServerGroup::OnRecv by IdBuf
  *                            (server/ServerGroup.cpp:44-60), SubGroup::OnRecv by (dst, conv)
  *                            (server/SubGroup.cpp:31-50), ClientGroup::OnRecv by conv (client/ClientGroup.cpp:66-80)
+ *   rsk_deliver_batch     <- the per-packet payload copy of the consumers: SConn::OnRecv
+ *                            (server/SConn.cpp:77-89), ClientGroup::send2Origin (client/ClientGroup.cpp:82-96)
  */
 #ifndef RSK_CODEC_H
 #define RSK_CODEC_H
@@ -475,6 +477,62 @@ typedef struct rsk_demux_out {
  * the first one's result to `out` before the second overwrites it. */
 int rsk_demux_batch(rsk_ctx *ctx, uint32_t n, const rsk_demux_in *in, uint32_t fields,
                     const rsk_demux_out *out, void *stream);
+
+/* ---- payload delivery: the VALID payloads packed in delivery order ------------------------------ */
+/* The reference's consumers copy every delivered payload on its own: SConn::OnRecv
+ * (server/SConn.cpp:77-89) and ClientGroup::send2Origin (client/ClientGroup.cpp:82-96) malloc +
+ * memcpy(base, rbuf.base, nread) and uv_udp_send it, where rbuf.base is the pointer RConn::OnRecv
+ * computed (conn/RConn.cpp:64-85: p = base + 8 + len, length nread - (p - base)).  rsk_deliver_batch is
+ * that copy for a batch: the payloads of the VALID packets gathered into one dense arena in delivery
+ * order, with the byte offset of every payload -- what completes "hands each conn its packets as one
+ * run" above: with order = the demux's perm, segment s is the bytes
+ * [out_off[seg_off[s]], out_off[seg_off[s + 1]]) of out_arena, so the host makes one contiguous D2H
+ * (or hands the arena to a next device stage) and one sendmmsg per segment with iovecs from out_off.
+ *
+ * Let m = n when order == NULL, else min(*n_order, n).  Position k < m stands for packet i = order[k]
+ * (k itself without an order) and has length L_k = pay_len[i] when i < n and status[i] ==
+ * RSK_RECV_VALID, else L_k = 0: a stray index, a packet that is not VALID, and every position of a
+ * poisoned n_valid of 0xFFFFFFFF (a look-back timeout, RSK_DEVERR_LOOKBACK) whose entry is stray, is
+ * skipped and its packet fields are never read (`order` must be readable for n entries, as perm and
+ * valid_idx are).
+ *   out_off[0] = 0, out_off[k + 1] = out_off[k] + roundup(L_k, align); every entry from m to n equals
+ *   the total, and *total = out_off[m].
+ *   Payload k is the L_k bytes at arena + base_off[i] + inner_off[i] + pay_off[i]; it lands at
+ *   out_arena + out_off[k], followed by zeros up to the rounded length.
+ * A payload whose rounded end exceeds out_cap is not written at all, and no byte at or past out_cap is
+ * written; *total still reports the need, so the caller compares it with out_cap (no device error bit).
+ * Every destination byte is written at most once, and nothing outside the rounded ranges is written.
+ * arena and out_arena must not overlap.  n <= 2^30.  RSK_EINVAL: a NULL in, out, out_off, base_off,
+ * pay_off, pay_len or status (the arrays may be NULL when n == 0), an align that is not a power of two
+ * in [1, 128], an out_arena that is not 16-B aligned, order / n_order not both set or both NULL.
+ * n == 0 writes out_off[0] = 0 and *total = 0.
+ * Scratch: 8 B per 1024 packets per stream (rsk_reserve_stream sizes it, so a call captured into a
+ * hipGraph after a reserve replays correctly: the launches are a linear chain and keep no host state). */
+typedef struct rsk_deliver_in {
+    const uint8_t  *arena;     /* device bytes the frames lie in: rsk_decode_batch's frame_arena,
+                                  rsk_parse_decode_batch's cap_arena, rsk_syncinput_decode_batch's rec_arena */
+    const uint64_t *base_off;  /* [n] frame_off / cap_off / rec_off                                  */
+    const uint16_t *inner_off; /* [n] tcp->cap_pay_off (frame start inside the capture / record), or NULL = 0 */
+    const uint16_t *pay_off;   /* [n] dec->pay_off                                                    */
+    const uint16_t *pay_len;   /* [n] dec->pay_len                                                    */
+    const int8_t   *status;    /* [n] dec->status; only RSK_RECV_VALID packets carry bytes            */
+    const uint32_t *order;     /* [*n_order] packet indices in delivery order: demux perm, or a decode's
+                                  valid_idx; NULL = 0..n-1                                            */
+    const uint32_t *n_order;   /* [1] device count (demux / decode n_valid); must be NULL iff order is */
+} rsk_deliver_in;
+typedef struct rsk_deliver_out {
+    uint8_t  *out_arena; /* device, 16-B aligned; NULL = plan only (offsets and total, no copy)       */
+    uint64_t  out_cap;   /* bytes available at out_arena                                              */
+    uint64_t *out_off;   /* [n+1] out_off[k] = start of the k-th delivered payload                    */
+    uint64_t *total;     /* [1] bytes needed (may be NULL)                                            */
+    uint32_t  align;     /* power of two in [1,128]: every payload starts at a multiple of it          */
+} rsk_deliver_out;
+int rsk_deliver_batch(rsk_ctx *ctx, uint32_t n, const rsk_deliver_in *in, const rsk_deliver_out *out,
+                      void *stream);
+/* Host twin (host pointers throughout; nthreads <= 1 runs on the caller's thread): the same offsets
+ * and bytes for host-resident deployments whose payloads never left host memory (the header-only
+ * batches above). */
+int rsk_deliver_host(uint32_t n, const rsk_deliver_in *in, const rsk_deliver_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

@@ -117,6 +117,16 @@ class DemuxOut(ctypes.Structure):
     _fields_ = [("perm", _vp), ("seg_off", _vp), ("seg_first", _vp), ("n_seg", _vp), ("n_valid", _vp)]
 
 
+class DeliverIn(ctypes.Structure):
+    _fields_ = [("arena", _vp), ("base_off", _vp), ("inner_off", _vp), ("pay_off", _vp), ("pay_len", _vp),
+                ("status", _vp), ("order", _vp), ("n_order", _vp)]
+
+
+class DeliverOut(ctypes.Structure):
+    _fields_ = [("out_arena", _vp), ("out_cap", ctypes.c_uint64), ("out_off", _vp), ("total", _vp),
+                ("align", ctypes.c_uint32)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -177,6 +187,10 @@ SIGNATURES = [
     ("rsk_tcp_recv_ack_batch", ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp]),
     ("rsk_demux_batch", ctypes.c_int,
      [_vp, ctypes.c_uint32, ctypes.POINTER(DemuxIn), ctypes.c_uint32, ctypes.POINTER(DemuxOut), _vp]),
+    ("rsk_deliver_batch", ctypes.c_int,
+     [_vp, ctypes.c_uint32, ctypes.POINTER(DeliverIn), ctypes.POINTER(DeliverOut), _vp]),
+    ("rsk_deliver_host", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.POINTER(DeliverIn), ctypes.POINTER(DeliverOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

@@ -193,6 +193,80 @@ class DemuxBuffers:
 
 
 @dataclass
+class DeliverBuffers:
+    """Outputs of rsk_deliver_batch for a batch of n packets (rsk_deliver_out): the dense payload
+    arena (`cap` bytes; None for a plan-only buffer set), out_off [n + 1] and total [1] (int64
+    storage of u64).  `cap` is the out_cap the next call passes (at most the arena's size)."""
+
+    arena: torch.Tensor | None
+    out_off: torch.Tensor
+    total: torch.Tensor
+    cap: int
+
+    @classmethod
+    def alloc(cls, n: int, device, cap: int = 0) -> "DeliverBuffers":
+        return cls(arena=torch.empty(cap, dtype=torch.uint8, device=device) if cap else None,
+                   out_off=torch.empty(n + 1, dtype=torch.int64, device=device),
+                   total=torch.empty(1, dtype=torch.int64, device=device), cap=int(cap))
+
+    def abi(self, align: int, plan_only: bool = False) -> _abi.DeliverOut:
+        arena = None if plan_only else self.arena
+        if arena is not None:
+            assert 0 <= self.cap <= arena.numel()
+        return _abi.DeliverOut(_ptr(arena), self.cap if arena is not None else 0, _ptr(self.out_off),
+                               _ptr(self.total), align)
+
+
+def segment_bytes(host_arena: np.ndarray, out_off, dmx, s: int) -> np.ndarray:
+    """Segment s of a delivery made with order = dmx.perm (a DemuxBuffers, or its seg_off as an
+    array), sliced out of a host copy of the delivered arena: the payloads of the segment's packets in
+    arrival order, back to back (each rounded up to the delivery's align)."""
+    seg_off = getattr(dmx, "seg_off", dmx)
+    lo, hi = (int(x) for x in seg_off[s:s + 2])
+    if isinstance(out_off, torch.Tensor):
+        out_off = out_off.cpu().numpy()
+    off = np.asarray(out_off).view(np.uint64)
+    return host_arena[int(off[lo]):int(off[hi])]
+
+
+def deliver_host(arena: np.ndarray, base_off: np.ndarray, pay_off: np.ndarray, pay_len: np.ndarray,
+                 status: np.ndarray, inner_off: np.ndarray | None = None, order: np.ndarray | None = None,
+                 n_order: int | None = None, align: int = 1, out: np.ndarray | None = None, cap: int | None = None,
+                 plan_only: bool = False, nthreads: int = 1):
+    """rsk_deliver_host on numpy arrays (no GPU): -> (out_arena or None, out_off uint64 [n + 1], total).
+    `out` is a 16-B aligned uint8 array to deliver into (cap defaults to its size); without one, the
+    call plans first and allocates exactly the total."""
+    n = len(status)
+    c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
+    arena, base_off, inner_off = c(arena, np.uint8), c(base_off, np.uint64), c(inner_off, np.uint16)
+    pay_off, pay_len, status, order = c(pay_off, np.uint16), c(pay_len, np.uint16), c(status, np.int8), c(order, np.uint32)
+    if (order is None) != (n_order is None):
+        raise RskError("rsk_deliver_host failed: rc=-22 (order and n_order go together)")
+    cnt = None if n_order is None else np.array([n_order], np.uint32)
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    din = _abi.DeliverIn(p(arena), p(base_off), p(inner_off), p(pay_off), p(pay_len), p(status), p(order), p(cnt))
+    off = np.empty(n + 1, np.uint64)
+    tot = np.zeros(1, np.uint64)
+
+    def call(dst, dcap):
+        dout = _abi.DeliverOut(p(dst), dcap, off.ctypes.data, tot.ctypes.data, align)
+        rc = lib().rsk_deliver_host(n, ctypes.byref(din), ctypes.byref(dout), nthreads)
+        if rc != 0:
+            raise RskError(f"rsk_deliver_host failed: rc={rc}")
+
+    if plan_only:
+        call(None, 0)
+        return None, off, int(tot[0])
+    if out is None:
+        call(None, 0)
+        raw = np.empty(int(tot[0]) + 16, np.uint8)
+        sh = (-raw.ctypes.data) % 16
+        out = raw[sh:sh + int(tot[0])]
+    call(out, len(out) if cap is None else cap)
+    return out, off, int(tot[0])
+
+
+@dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
 
@@ -326,7 +400,7 @@ class Codec:
         _check(lib().rsk_release_stream(self._ctx, _stream(stream)), "rsk_release_stream")
 
     def reserve(self, n_max: int, stream=None) -> None:
-        """Pre-size the compaction scratch of `stream` (default: torch's current stream)."""
+        """Pre-size the compaction and delivery scratch of `stream` (default: torch's current stream)."""
         _check(lib().rsk_reserve_stream(self._ctx, n_max, _stream(stream)), "rsk_reserve_stream")
 
     # ---- batch paths ---------------------------------------------------------------------
@@ -469,6 +543,21 @@ class Codec:
         din = _abi.DemuxIn(_ptr(status), _ptr(cmd), _ptr(id), _ptr(conv), _ptr(conn_key), _ptr(dst))
         _check(lib().rsk_demux_batch(self._ctx, n, ctypes.byref(din), fields, ctypes.byref(out.abi()),
                                      _stream(stream)), "rsk_demux_batch")
+
+    def deliver_batch(self, arena, base_off, pay_off, pay_len, status, out: "DeliverBuffers", inner_off=None,
+                      order=None, n_order=None, align: int = 1, plan_only: bool = False, stream=None) -> None:
+        """The consumers' per-packet payload copy (SConn::OnRecv, server/SConn.cpp:77-89), batched
+        (rsk_deliver_batch): the VALID payloads at arena + base_off + inner_off + pay_off packed into
+        out.arena in `order` (a demux's perm with its n_valid, a decode's valid_idx with its n_valid, or
+        None = packet order), payload k at out.out_off[k], each rounded up to `align`; out.total is the
+        bytes needed, to compare with out.cap.  plan_only (or an `out` without an arena) writes the
+        offsets and the total only."""
+        n = status.numel()
+        din = _abi.DeliverIn(_ptr(arena), _ptr(base_off), _ptr(inner_off), _ptr(pay_off), _ptr(pay_len),
+                             _ptr(status), _ptr(order), _ptr(n_order))
+        dout = out.abi(align, plan_only)
+        _check(lib().rsk_deliver_batch(self._ctx, n, ctypes.byref(din), ctypes.byref(dout), _stream(stream)),
+               "rsk_deliver_batch")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

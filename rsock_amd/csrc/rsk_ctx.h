@@ -1,5 +1,5 @@
 // Internal (not installed): the rsk_ctx handle and host helpers shared by the librsk translation
-// units (rsk_kernels.hip: codec; rsk_demux.hip: receive demux).
+// units (rsk_kernels.hip: codec; rsk_demux.hip: receive demux; rsk_deliver.hip: payload delivery).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,7 +19,10 @@ struct ShimIO;  // rsk_kernels.hip
 
 namespace rsk {
 // Device scratch of one kind for the calls ordered on one stream.
-enum WsKind { WS_COMPACT = 0, WS_SEQ = 1, WS_DEMUX = 2, WS_ENC = 3, WS_KINDS = 4 };
+enum WsKind { WS_COMPACT = 0, WS_SEQ = 1, WS_DEMUX = 2, WS_ENC = 3, WS_DELIVER = 4, WS_KINDS = 5 };
+// WS_DELIVER (rsk_deliver.hip): one 64-bit sum per tile of kDeliverTile positions, and the total
+constexpr uint32_t kDeliverTile = 1024;
+inline size_t deliver_ws_bytes(uint32_t n) { return ((size_t)(n + kDeliverTile - 1u) / kDeliverTile + 1u) * 8u; }
 struct WsBuf {
     void *p = nullptr;
     size_t bytes = 0;

@@ -1,6 +1,7 @@
 // rsk_host.cpp — host-side batch helpers of the header-only path (include/rsk_codec.h): staging
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
-// payloads, each over contiguous shards on std::threads.  Pure host code (no HIP calls).
+// payloads, each over contiguous shards on std::threads; and the host twin of the payload delivery
+// (rsk_deliver_host).  Pure host code (no HIP calls).
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -44,6 +45,50 @@ extern "C" int rsk_assemble_frames(uint32_t n, const uint8_t *hdr, const int32_t
             uint8_t *f = frame_arena + frame_off[i];
             std::memcpy(f, hdr + 32ull * i, RSK_HEAD_SIZE);                                   // RConn.cpp:101-103
             std::memcpy(f + RSK_HEAD_SIZE, payload_arena + pay_off[i], (size_t)(st - RSK_HEAD_SIZE));  // :104
+        }
+    });
+    return RSK_OK;
+}
+
+// rsk_deliver_batch on host pointers: the copy SConn::OnRecv (server/SConn.cpp:77-89) and
+// ClientGroup::send2Origin (client/ClientGroup.cpp:82-96) make per packet, into one dense arena.  The
+// offsets are one serial prefix sum; the copies run over contiguous shards of positions.
+extern "C" int rsk_deliver_host(uint32_t n, const rsk_deliver_in *in, const rsk_deliver_out *out, int nthreads) {
+    if (!in || !out || !out->out_off) return RSK_EINVAL;
+    const uint32_t al = out->align;
+    if (al == 0u || al > 128u || (al & (al - 1u))) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(out->out_arena) & 15u) return RSK_EINVAL;
+    if ((in->order == nullptr) != (in->n_order == nullptr)) return RSK_EINVAL;
+    if (n && (!in->base_off || !in->pay_off || !in->pay_len || !in->status)) return RSK_EINVAL;
+    if (n && out->out_arena && !in->arena) return RSK_EINVAL;
+    if (n > (1u << 30)) return RSK_EINVAL;
+    const uint32_t m = in->order ? (*in->n_order < n ? *in->n_order : n) : n;
+    // packet of position k, or n when the position carries no bytes
+    auto index = [=](uint32_t k) -> uint32_t {
+        const uint32_t i = in->order ? in->order[k] : k;
+        return i < n && in->status[i] == RSK_RECV_VALID ? i : n;
+    };
+    uint64_t *off = out->out_off;
+    uint64_t run = 0;
+    for (uint32_t k = 0; k < m; ++k) {
+        off[k] = run;
+        const uint32_t i = index(k);
+        if (i < n) run += ((uint64_t)in->pay_len[i] + al - 1u) & ~(uint64_t)(al - 1u);
+    }
+    for (uint32_t k = m; k <= n; ++k) off[k] = run;
+    if (out->total) *out->total = run;
+    if (!out->out_arena) return RSK_OK;
+    uint8_t *dst = out->out_arena;
+    const uint64_t cap = out->out_cap;
+    for_shards(m, nthreads, [=](uint32_t lo, uint32_t hi) {
+        for (uint32_t k = lo; k < hi; ++k) {
+            const uint64_t r = off[k + 1] - off[k];
+            if (r == 0 || off[k + 1] > cap) continue;  // nothing to write, or cut by out_cap: not written at all
+            const uint32_t i = index(k);
+            const size_t len = in->pay_len[i];
+            const uint8_t *src = in->arena + in->base_off[i] + (in->inner_off ? in->inner_off[i] : 0u) + in->pay_off[i];
+            std::memcpy(dst + off[k], src, len);  // RConn.cpp:64-85's pointer, SConn.cpp:80's memcpy
+            std::memset(dst + off[k] + len, 0, (size_t)r - len);
         }
     });
     return RSK_OK;

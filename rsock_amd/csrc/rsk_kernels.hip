@@ -3186,7 +3186,13 @@ int rsk_reserve_stream(rsk_ctx *c, uint32_t n_max, void *stream) {
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
     Compact ck;
-    const int r = ensure_compact(c, n_max, (hipStream_t)stream, ck);
+    int r = ensure_compact(c, n_max, (hipStream_t)stream, ck);
+    // the delivery's tile sums (rsk_deliver.hip: 8 B per 1024 packets), so that a captured
+    // rsk_deliver_batch finds them
+    if (!r && n_max <= (1u << 30)) {
+        void *dl = nullptr;
+        r = rsk::stream_ws(c, (hipStream_t)stream, rsk::WS_DELIVER, rsk::deliver_ws_bytes(n_max), &dl);
+    }
     // the two-pass encode's header records (32 B per packet), for a context that encodes: held to the
     // two-pass path, or AUTO with an encode call behind it (a decode- or demux-only context
     // does not pay 32 B per packet for them).  A capture cannot allocate them: without this reserve

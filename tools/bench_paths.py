@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-path kernel timings on one config (device-resident, HIP events, interleaved rounds in one
 process): encode (framing), encode_wire RAW4 / Ethernet (framing + IPv4/TCP build + checksums),
-decode (verify + compaction), parse_decode (pcap parse of the Ethernet wire packets + verify).
+decode (verify + compaction), parse_decode (pcap parse of the Ethernet wire packets + verify), ...,
+deliver / deliver_demux / deliver_plan (the VALID payloads packed in valid_idx / demux order; offsets only).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -23,6 +24,9 @@ def main():
                     help="wire packet pitch alignment (bytes); 0 = the frame slot rule (128 with PAD128 for "
                          "mixed lengths, else 16)")
     ap.add_argument("--only", default="", help="time only these paths (comma list), e.g. demux,demux_64conn")
+    ap.add_argument("--copy-yardstick", action="store_true",
+                    help="also time tools/libhbm_probe.so's dense 16-B copy of the delivered byte count (rows "
+                         "dense_copy@GRID) and report deliver's time over the fastest of them")
     ap.add_argument("--encode-path", type=int, default=0,
                     help="rsk_set_encode_path for the encode paths: 0 chosen per call, 1 k_encode, 2 two-pass, 3 short")
     args = ap.parse_args()
@@ -169,6 +173,49 @@ def main():
     hlen = w.frame_len.to(torch.int32) + 21
     tcp3, sdec = rc.TcpInfoBuffers.alloc(n, dev), rc.DecodeBuffers.alloc(n, dev)
     ops["syncinput_decode"] = lambda: cx.syncinput_batch(hand, hoff, hlen, tcp3, sdec, stream=s)
+    # payload delivery (rsk_deliver_batch) of the decoded batch: the VALID payloads packed in valid_idx
+    # order, in the segment order of the ALL | CMD_BARRIER demux, and the offsets alone
+    # (decoded into buffers of its own with the config's corrupted frames -- C4: 1 in 16 dropped -- and
+    # the frames restored, so the rows do not depend on which of the ops above ran last)
+    ddec = rc.DecodeBuffers.alloc(n, dev)
+    w.corrupt_frames()
+    cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, ddec, stream=s)
+    w.corrupt_frames()
+    dmxa = rc.DemuxBuffers.alloc(n, dev)
+    afields = A.DEMUX_ID | A.DEMUX_CONN_KEY | A.DEMUX_CONV | A.DEMUX_DST | A.DEMUX_CMD_BARRIER
+    zdst = torch.zeros(n, dtype=torch.int32, device=dev)
+    cx_all = rc.Codec(b"hello135", 0)
+    cx_all.demux_batch(ddec.status, ddec.cmd, afields, dmxa, id=ddec.id, conv=ddec.conv, conn_key=ddec.conn_key,
+                       dst=zdst, stream=s)
+    plan = rc.DeliverBuffers.alloc(n, dev)
+    dl_in = (w.frame, w.frame_off, ddec.pay_off, ddec.pay_len, ddec.status)
+    cx.deliver_batch(*dl_in, plan, order=ddec.valid_idx, n_order=ddec.n_valid, stream=s)
+    torch.cuda.synchronize()
+    dl_bytes = int(plan.total.item())
+    dlv = rc.DeliverBuffers.alloc(n, dev, max(dl_bytes, 16))
+    ops["deliver"] = lambda: cx.deliver_batch(*dl_in, dlv, order=ddec.valid_idx, n_order=ddec.n_valid, stream=s)
+    ops["deliver_demux"] = lambda: cx.deliver_batch(*dl_in, dlv, order=dmxa.perm, n_order=dmxa.n_valid, stream=s)
+    ops["deliver_plan"] = lambda: cx.deliver_batch(*dl_in, plan, order=ddec.valid_idx, n_order=ddec.n_valid,
+                                                   stream=s)
+    # the same delivery with every payload on a 16-B boundary: whole-chunk stores only (what the byte
+    # borders of align = 1 cost is deliver's time over this row's)
+    cx.deliver_batch(*dl_in, plan, order=ddec.valid_idx, n_order=ddec.n_valid, align=16, stream=s)
+    torch.cuda.synchronize()
+    dl16_bytes = int(plan.total.item())
+    dlv16 = rc.DeliverBuffers.alloc(n, dev, max(dl16_bytes, 16))
+    ops["deliver_align16"] = lambda: cx.deliver_batch(*dl_in, dlv16, order=ddec.valid_idx, n_order=ddec.n_valid,
+                                                      align=16, stream=s)
+    if args.copy_yardstick:
+        # the dense 16-B copy of tools/hbm_probe.hip over the delivered byte count, in this process
+        import ctypes
+
+        hp = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhbm_probe.so"))
+        hp.probe_run.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                 ctypes.c_void_p]
+        ysrc = torch.randint(0, 255, (dl_bytes + 16,), dtype=torch.uint8, device=dev)
+        for grid in (2048, 8192, 65536):
+            ops[f"dense_copy@{grid}"] = lambda grid=grid: hp.probe_run(0, ysrc.data_ptr(), dlv.arena.data_ptr(),
+                                                                       dl_bytes, grid, s.cuda_stream)
     nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -208,7 +255,13 @@ def main():
         "tcp_recv_ack": 4 + 1 + 4,      # conn, delivered, seq in
         # record bytes [0, 53) + rec_off + nread in; TcpInfo (26) + decode fields (27) + valid_idx out
         "syncinput_decode": 53 + 8 + 4 + 26 + 27 + 4,
+        # payload bytes read + written, + 8 B per offset
+        "deliver": 2 * dl_bytes / n + 8,
+        "deliver_demux": 2 * dl_bytes / n + 8,
+        "deliver_plan": 8,
+        "deliver_align16": (dl_bytes + dl16_bytes) / n + 8,
     }
+    alg.update({k: 2 * dl_bytes / n for k in ops if k.startswith("dense_copy@")})
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -218,8 +271,15 @@ def main():
         m = float(np.median(t))
         a = alg.get(k, alg["encode_wire_eth" if "_eth_" in k else "encode_wire_raw4"])
         out[k] = {"ms": round(m, 4), "Mpkt_s": round(n / m / 1e3, 1), "GBps_alg": round(n * a / m / 1e6, 1)}
-    print(json.dumps({"config": args.config, "packets": n, "wire_pitch": [p4, pe], "demux_segments": nseg,
-                      "paths": out}))
+    res = {"config": args.config, "packets": n, "wire_pitch": [p4, pe], "demux_segments": nseg,
+           "deliver_bytes": dl_bytes, "paths": out}
+    dense = [v["ms"] for k, v in out.items() if k.startswith("dense_copy@")]
+    if dense and "deliver" in out:
+        res["dense_copy_ms"] = min(dense)
+        res["deliver_over_dense_copy"] = round(out["deliver"]["ms"] / min(dense), 3)
+        if "deliver_demux" in out:
+            res["deliver_demux_over_dense_copy"] = round(out["deliver_demux"]["ms"] / min(dense), 3)
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
