@@ -73,6 +73,9 @@ extern "C" {
 /* pcap datalink types accepted by RawTcp::RawInput (RawTcp.cpp:144-165) */
 #define RSK_DLT_NULL 0
 #define RSK_DLT_EN10MB 1
+/* The packet starts at the IPv4 header (pcap DLT_RAW; the LIBNET_RAW4 layout rsk_encode_wire_batch
+ * writes with with_eth = 0).  rsk_verify_wire_batch only: the parse and filter entry points reject it. */
+#define RSK_DLT_RAW 12
 
 /* ---- error codes returned by every entry point --------------------------------------------- */
 #define RSK_OK 0
@@ -533,6 +536,68 @@ int rsk_deliver_batch(rsk_ctx *ctx, uint32_t n, const rsk_deliver_in *in, const 
  * and bytes for host-resident deployments whose payloads never left host memory (the header-only
  * batches above). */
 int rsk_deliver_host(uint32_t n, const rsk_deliver_in *in, const rsk_deliver_out *out, int nthreads);
+
+/* ---- checksum verification of captured packets --------------------------------------------------- */
+/* rsock's fake-TCP segments reach RawTcp::RawInput (conn/RawTcp.cpp:138-237) through libpcap, before
+ * the kernel's TCP input path has verified or dropped them, and the frame's tag covers payload[0]
+ * only.  rsk_verify_wire_batch checks the IPv4 header checksum and the TCP checksum of every captured
+ * packet -- the other half of rsk_encode_wire_batch, which fills both in.  It belongs behind the
+ * capture filter and the parse: parse_decode -> verify(status = dec->status, status_out =
+ * dec->status) -> demux -> deliver.  (Packets a host sends itself with checksum offload are captured
+ * with unfinished checksums and fail the check.)
+ *
+ * Packet i is the c = cap_len[i] bytes at p = cap_arena + cap_off[i]; L = 14 (RSK_DLT_EN10MB), 4
+ * (RSK_DLT_NULL) or 0 (RSK_DLT_RAW); integers big-endian unless stated.
+ *   0. in->status given and status[i] != RSK_RECV_VALID: csum[i] = 0, no byte of the packet is read.
+ *   1. Link: EN10MB needs c >= 14 and p[12..13] == 08 00; NULL needs c >= 4 and the little-endian
+ *      u32 at p == 2; RAW has no link check.  Otherwise csum[i] = 0.
+ *   2. Header: c >= L + 20, p[L] >> 4 == 4, ihl = p[L] & 15 >= 5, H = 4 * ihl, c >= L + H.
+ *      Otherwise csum[i] = 0.
+ *   3. IP_CHECKED is set; IP_OK iff the ones'-complement sum of the header's H / 2 halfwords folds
+ *      to 0xFFFF.
+ *   4. TCP is attempted iff p[L + 9] == 6, (u16 at p + L + 6) & 0x3FFF == 0 (MF clear, fragment
+ *      offset 0) and tot = u16 at p + L + 2 >= H + 20; otherwise no TCP bit is set.
+ *   5. L + tot > c: TCP_TRUNC is set and neither other TCP bit.
+ *   6. Otherwise, with T = tot - H: TCP_CHECKED is set; TCP_OK iff the source and destination address
+ *      halfwords + 6 + T + the halfwords of the T segment bytes (an odd last byte taken as the high
+ *      byte) fold to 0xFFFF.  The data offset is not consulted: the checksum covers the whole segment.
+ *      The TCP check runs whether or not IP_OK is set.
+ * Bytes at or past p + L + tot (Ethernet trailer padding, the next packet) are never summed, and
+ * cap_len bounds every read: no 16-B aligned chunk without a byte of [p, p + c) is loaded, so the arena
+ * may end at the last packet's last byte.  A field that holds 0xFFFF where 0x0000 is correct still
+ * folds to 0xFFFF and is accepted, as Linux accepts it.
+ * A packet is bad iff (IP_CHECKED && !IP_OK) || (TCP_CHECKED && !TCP_OK); "not checkable" is never
+ * bad (the caller reads csum to be stricter).  status_out[i] = RSK_RECV_DROP when status[i] ==
+ * RSK_RECV_VALID and the packet is bad, else status[i]; *n_bad = the number of bad packets (written,
+ * not accumulated).
+ * RSK_EINVAL: a NULL ctx, in or out; a NULL csum, cap_arena, cap_off or cap_len with n > 0; status_out
+ * without in->status; a datalink outside {RSK_DLT_NULL, RSK_DLT_EN10MB, RSK_DLT_RAW}; n >
+ * RSK_VERIFY_MAX_BATCH (8 work-items per packet in blocks of 256: a grid holds at most 2^32 - 1,
+ * DESIGN.md §4.10).  n == 0 is a no-op that zeroes a given n_bad.
+ * No scratch: one memset node (n_bad, when given) and one kernel, a linear chain that a hipGraph
+ * captures without a reserve; no device-error bit is set. */
+#define RSK_CSUM_IP_CHECKED  0x01u
+#define RSK_CSUM_IP_OK       0x02u
+#define RSK_CSUM_TCP_CHECKED 0x04u
+#define RSK_CSUM_TCP_OK      0x08u
+#define RSK_CSUM_TCP_TRUNC   0x10u /* the TCP segment runs past cap_len (snaplen): not checkable */
+#define RSK_VERIFY_MAX_BATCH 0x1FFFFFE0u /* 2^29 - 32 */
+typedef struct rsk_verify_in {
+    const uint8_t  *cap_arena;  /* as rsk_parse_decode_batch                                          */
+    const uint64_t *cap_off;    /* [n]                                                                */
+    const uint32_t *cap_len;    /* [n]                                                                */
+    const int8_t   *status;     /* [n] optional (dec->status): when set, only RSK_RECV_VALID packets are examined */
+} rsk_verify_in;
+typedef struct rsk_verify_out {
+    uint8_t  *csum;        /* [n] RSK_CSUM_* bits, 0 = not examined / not IPv4                        */
+    int8_t   *status_out;  /* [n] optional; requires in->status; may be the SAME pointer as in->status */
+    uint32_t *n_bad;       /* [1] optional device count of bad packets (written, not accumulated)     */
+} rsk_verify_out;
+int rsk_verify_wire_batch(rsk_ctx *ctx, uint32_t n, const rsk_verify_in *in, int datalink,
+                          const rsk_verify_out *out, void *stream);
+/* Host twin (host pointers throughout; the same rule and outputs; nthreads as rsk_deliver_host; no
+ * upper limit on n). */
+int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, const rsk_verify_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

@@ -26,6 +26,7 @@ TCPINFO_WIRE_SIZE = 21
 CMD_DATA, CMD_CONV_RST, CMD_NETCONN_RST, CMD_KEEP_ALIVE_REQ, CMD_KEEP_ALIVE_RESP = 0, 1, 2, 3, 4
 TH_FIN, TH_SYN, TH_RST, TH_PUSH, TH_ACK = 0x01, 0x02, 0x04, 0x08, 0x10
 DLT_NULL, DLT_EN10MB = 0, 1
+DLT_RAW = 12  # the packet starts at the IPv4 header; rsk_verify_wire_batch only
 
 OK, EINVAL, ENOMEM, EDEVICE = 0, -22, -12, -5
 SEND_OVERSIZE, SEND_RESET = -1, 0
@@ -40,6 +41,8 @@ DEVERR_LOOKBACK = 0x1
 DEVERR_TABLE = 0x2
 DEMUX_ID, DEMUX_CONN_KEY, DEMUX_CONV, DEMUX_DST, DEMUX_CMD_BARRIER = 0x01, 0x02, 0x04, 0x08, 0x10
 DEMUX_GROUP_BARRIER = 0x20
+CSUM_IP_CHECKED, CSUM_IP_OK, CSUM_TCP_CHECKED, CSUM_TCP_OK, CSUM_TCP_TRUNC = 0x01, 0x02, 0x04, 0x08, 0x10
+VERIFY_MAX_BATCH = 0x1FFFFFE0
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -127,6 +130,14 @@ class DeliverOut(ctypes.Structure):
                 ("align", ctypes.c_uint32)]
 
 
+class VerifyIn(ctypes.Structure):
+    _fields_ = [("cap_arena", _vp), ("cap_off", _vp), ("cap_len", _vp), ("status", _vp)]
+
+
+class VerifyOut(ctypes.Structure):
+    _fields_ = [("csum", _vp), ("status_out", _vp), ("n_bad", _vp)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -191,6 +202,10 @@ SIGNATURES = [
      [_vp, ctypes.c_uint32, ctypes.POINTER(DeliverIn), ctypes.POINTER(DeliverOut), _vp]),
     ("rsk_deliver_host", ctypes.c_int,
      [ctypes.c_uint32, ctypes.POINTER(DeliverIn), ctypes.POINTER(DeliverOut), ctypes.c_int]),
+    ("rsk_verify_wire_batch", ctypes.c_int,
+     [_vp, ctypes.c_uint32, ctypes.POINTER(VerifyIn), ctypes.c_int, ctypes.POINTER(VerifyOut), _vp]),
+    ("rsk_verify_wire_host", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.POINTER(VerifyIn), ctypes.c_int, ctypes.POINTER(VerifyOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

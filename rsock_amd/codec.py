@@ -266,6 +266,26 @@ def deliver_host(arena: np.ndarray, base_off: np.ndarray, pay_off: np.ndarray, p
     return out, off, int(tot[0])
 
 
+def verify_wire_host(cap: np.ndarray, cap_off: np.ndarray, cap_len: np.ndarray, datalink: int,
+                     status: np.ndarray | None = None, want_status_out: bool = False, nthreads: int = 1):
+    """rsk_verify_wire_host on numpy arrays (no GPU): -> (csum uint8 [n], status_out int8 [n] or None,
+    n_bad).  `status` gates the check to its RSK_RECV_VALID packets; want_status_out (needs `status`)
+    also returns the status with the bad packets dropped."""
+    n = len(cap_len)
+    c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
+    cap, cap_off, cap_len, status = c(cap, np.uint8), c(cap_off, np.uint64), c(cap_len, np.uint32), c(status, np.int8)
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    csum = np.full(max(n, 1), 0xEE, np.uint8)
+    sout = np.full(max(n, 1), 0x55, np.int8) if want_status_out else None
+    nb = np.full(1, 0xFFFFFFFF, np.uint32)
+    vin = _abi.VerifyIn(p(cap), p(cap_off), p(cap_len), p(status))
+    vout = _abi.VerifyOut(p(csum), p(sout), p(nb))
+    rc = lib().rsk_verify_wire_host(n, ctypes.byref(vin), datalink, ctypes.byref(vout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_verify_wire_host failed: rc={rc}")
+    return csum[:n], None if sout is None else sout[:n], int(nb[0])
+
+
 @dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
@@ -558,6 +578,19 @@ class Codec:
         dout = out.abi(align, plan_only)
         _check(lib().rsk_deliver_batch(self._ctx, n, ctypes.byref(din), ctypes.byref(dout), _stream(stream)),
                "rsk_deliver_batch")
+
+    def verify_wire_batch(self, cap, cap_off, cap_len, datalink: int, csum, status=None, status_out=None,
+                          n_bad=None, stream=None) -> None:
+        """IPv4 header and TCP checksum check of n captured packets (rsk_verify_wire_batch): csum[i]
+        gets the CSUM_* bits of packet i (cap_len[i] bytes at cap + cap_off[i]; datalink DLT_EN10MB,
+        DLT_NULL or DLT_RAW).  With `status` (a decode's status) only the RECV_VALID packets are
+        examined; status_out (may be `status` itself) gets the status with the bad packets set to
+        RECV_DROP, n_bad [1] their number."""
+        n = cap_len.numel()
+        vin = _abi.VerifyIn(_ptr(cap), _ptr(cap_off), _ptr(cap_len), _ptr(status))
+        vout = _abi.VerifyOut(_ptr(csum), _ptr(status_out), _ptr(n_bad))
+        _check(lib().rsk_verify_wire_batch(self._ctx, n, ctypes.byref(vin), datalink, ctypes.byref(vout),
+                                           _stream(stream)), "rsk_verify_wire_batch")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

@@ -1,7 +1,9 @@
 // rsk_host.cpp — host-side batch helpers of the header-only path (include/rsk_codec.h): staging
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
-// payloads, each over contiguous shards on std::threads; and the host twin of the payload delivery
-// (rsk_deliver_host).  Pure host code (no HIP calls).
+// payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
+// (rsk_deliver_host) and of the checksum verification (rsk_verify_wire_host).  Pure host code (no HIP
+// calls).
+#include <atomic>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -91,6 +93,80 @@ extern "C" int rsk_deliver_host(uint32_t n, const rsk_deliver_in *in, const rsk_
             std::memset(dst + off[k] + len, 0, (size_t)r - len);
         }
     });
+    return RSK_OK;
+}
+
+namespace {
+
+uint32_t fold16(uint64_t s) {
+    while (s >> 16) s = (s & 0xffffu) + (s >> 16);
+    return (uint32_t)s;
+}
+
+// Ones'-complement sum of the len bytes at p as big-endian halfwords (an odd last byte is the high
+// byte), folded to 16 bits.  Sums little-endian 32-bit words from p on -- the packet's halfwords
+// byte-swapped -- and swaps the folded result once (RFC 1071 §2(B)).
+uint32_t sum_be16(const uint8_t *p, size_t len) {
+    uint64_t s = 0;
+    size_t k = 0;
+    for (; k + 4 <= len; k += 4) {
+        uint32_t w;
+        std::memcpy(&w, p + k, 4);
+        s += w;
+    }
+    uint32_t tail = 0;
+    std::memcpy(&tail, p + k, len - k);
+    const uint32_t f = fold16(s + tail);
+    return ((f & 0xffu) << 8) | (f >> 8);
+}
+
+// RSK_CSUM_* bits of one captured packet (the rule of rsk_verify_wire_batch, include/rsk_codec.h)
+uint32_t verify_one(const uint8_t *p, uint32_t c, uint32_t L) {
+    if (L == 14 && !(c >= 14 && p[12] == 0x08 && p[13] == 0x00)) return 0;
+    if (L == 4 && !(c >= 4 && p[0] == 2 && p[1] == 0 && p[2] == 0 && p[3] == 0)) return 0;
+    if (c < L + 20) return 0;
+    const uint8_t *ip = p + L;
+    const uint32_t ihl = ip[0] & 15u, H = 4 * ihl;
+    if ((ip[0] >> 4) != 4 || ihl < 5 || c < L + H) return 0;
+    uint32_t f = RSK_CSUM_IP_CHECKED;
+    if (sum_be16(ip, H) == 0xffffu) f |= RSK_CSUM_IP_OK;
+    const uint32_t tot = ((uint32_t)ip[2] << 8) | ip[3], frag = ((uint32_t)ip[6] << 8) | ip[7];
+    if (ip[9] != 6 || (frag & 0x3fffu) || tot < H + 20) return f;
+    if (L + tot > c) return f | RSK_CSUM_TCP_TRUNC;
+    const uint32_t T = tot - H;
+    f |= RSK_CSUM_TCP_CHECKED;
+    if (fold16((uint64_t)sum_be16(ip + 12, 8) + 6u + T + sum_be16(ip + H, T)) == 0xffffu) f |= RSK_CSUM_TCP_OK;
+    return f;
+}
+
+}  // namespace
+
+// rsk_verify_wire_batch on host pointers, over contiguous shards of packets.
+extern "C" int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, const rsk_verify_out *out,
+                                    int nthreads) {
+    if (!in || !out) return RSK_EINVAL;
+    if (datalink != RSK_DLT_NULL && datalink != RSK_DLT_EN10MB && datalink != RSK_DLT_RAW) return RSK_EINVAL;
+    if (out->status_out && !in->status) return RSK_EINVAL;
+    if (n && (!in->cap_arena || !in->cap_off || !in->cap_len || !out->csum)) return RSK_EINVAL;
+    const uint32_t L = datalink == RSK_DLT_EN10MB ? 14u : datalink == RSK_DLT_NULL ? 4u : 0u;
+    std::atomic<uint32_t> bad_total{0};
+    std::atomic<uint32_t> *bt = &bad_total;
+    const rsk_verify_in a = *in;
+    const rsk_verify_out o = *out;
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        uint32_t nb = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const int8_t st = a.status ? a.status[i] : (int8_t)RSK_RECV_VALID;
+            const uint32_t f = st == RSK_RECV_VALID ? verify_one(a.cap_arena + a.cap_off[i], a.cap_len[i], L) : 0u;
+            const bool bad = ((f & RSK_CSUM_IP_CHECKED) && !(f & RSK_CSUM_IP_OK)) ||
+                             ((f & RSK_CSUM_TCP_CHECKED) && !(f & RSK_CSUM_TCP_OK));
+            o.csum[i] = (uint8_t)f;
+            if (o.status_out) o.status_out[i] = bad ? (int8_t)RSK_RECV_DROP : st;
+            nb += bad;
+        }
+        bt->fetch_add(nb, std::memory_order_relaxed);
+    });
+    if (out->n_bad) *out->n_bad = bad_total.load();
     return RSK_OK;
 }
 

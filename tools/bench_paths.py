@@ -2,7 +2,8 @@
 """Per-path kernel timings on one config (device-resident, HIP events, interleaved rounds in one
 process): encode (framing), encode_wire RAW4 / Ethernet (framing + IPv4/TCP build + checksums),
 decode (verify + compaction), parse_decode (pcap parse of the Ethernet wire packets + verify), ...,
-deliver / deliver_demux / deliver_plan (the VALID payloads packed in valid_idx / demux order; offsets only).
+deliver / deliver_demux / deliver_plan (the VALID payloads packed in valid_idx / demux order; offsets only),
+verify_wire_eth / verify_wire_raw4 (IPv4 + TCP checksum check of the wire packets built above).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -27,6 +28,9 @@ def main():
     ap.add_argument("--copy-yardstick", action="store_true",
                     help="also time tools/libhbm_probe.so's dense 16-B copy of the delivered byte count (rows "
                          "dense_copy@GRID) and report deliver's time over the fastest of them")
+    ap.add_argument("--read-yardstick", action="store_true",
+                    help="also time tools/libhbm_probe.so's dense 16-B read of the byte count verify_wire_eth sums "
+                         "(rows dense_read@GRID) and report the verify rows' times over the fastest of them")
     ap.add_argument("--encode-path", type=int, default=0,
                     help="rsk_set_encode_path for the encode paths: 0 chosen per call, 1 k_encode, 2 two-pass, 3 short")
     args = ap.parse_args()
@@ -216,6 +220,31 @@ def main():
         for grid in (2048, 8192, 65536):
             ops[f"dense_copy@{grid}"] = lambda grid=grid: hp.probe_run(0, ysrc.data_ptr(), dlv.arena.data_ptr(),
                                                                        dl_bytes, grid, s.cuda_stream)
+    # checksum verification (rsk_verify_wire_batch) of the wire packets built above: link header + IPv4
+    # total length read per packet, one flag byte written
+    vcs = torch.empty(n, dtype=torch.uint8, device=dev)
+    vnb = torch.empty(1, dtype=torch.int32, device=dev)
+    ops["verify_wire_eth"] = lambda: cx.verify_wire_batch(wiree, offe, ste, A.DLT_EN10MB, vcs, n_bad=vnb, stream=s)
+    ops["verify_wire_raw4"] = lambda: cx.verify_wire_batch(wire4, off4, st4, A.DLT_RAW, vcs, n_bad=vnb, stream=s)
+    vf_bytes = {"eth": int(ste.clamp(min=0).sum().item()), "raw4": int(st4.clamp(min=0).sum().item())}
+    for k, (st_k, dl) in {"verify_wire_eth": (ste, A.DLT_EN10MB), "verify_wire_raw4": (st4, A.DLT_RAW)}.items():
+        ops[k]()
+        torch.cuda.synchronize()
+        written = st_k > 0
+        assert int(vnb.item()) == 0 and bool((vcs[written] == 0x0F).all()) and bool((vcs[~written] == 0).all()), k
+    if args.read_yardstick:
+        # the dense 16-B read of tools/hbm_probe.hip (k_read16) over the Ethernet rows' byte count, in
+        # this process: the wire arena's own first bytes
+        import ctypes
+
+        hp = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhbm_probe.so"))
+        hp.probe_run.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                 ctypes.c_void_p]
+        ysink = torch.zeros(16, dtype=torch.int32, device=dev)
+        assert vf_bytes["eth"] <= wiree.numel()
+        for grid in (2048, 8192, 65536):
+            ops[f"dense_read@{grid}"] = lambda grid=grid: hp.probe_run(1, wiree.data_ptr(), ysink.data_ptr(),
+                                                                       vf_bytes["eth"], grid, s.cuda_stream)
     nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -262,6 +291,9 @@ def main():
         "deliver_align16": (dl_bytes + dl16_bytes) / n + 8,
     }
     alg.update({k: 2 * dl_bytes / n for k in ops if k.startswith("dense_copy@")})
+    # verify: link header + IPv4 total length read, one flag byte written
+    alg.update({"verify_wire_eth": vf_bytes["eth"] / n + 1, "verify_wire_raw4": vf_bytes["raw4"] / n + 1})
+    alg.update({k: vf_bytes["eth"] / n for k in ops if k.startswith("dense_read@")})
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -279,6 +311,13 @@ def main():
         res["deliver_over_dense_copy"] = round(out["deliver"]["ms"] / min(dense), 3)
         if "deliver_demux" in out:
             res["deliver_demux_over_dense_copy"] = round(out["deliver_demux"]["ms"] / min(dense), 3)
+    dread = [v["ms"] for k, v in out.items() if k.startswith("dense_read@")]
+    if dread:
+        res["verify_bytes"] = vf_bytes
+        res["dense_read_ms"] = min(dread)
+        for k in ("verify_wire_eth", "verify_wire_raw4"):
+            if k in out:
+                res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dread), 3)
     print(json.dumps(res))
 
 
