@@ -1,10 +1,11 @@
 // rsk_host.cpp — host-side batch helpers of the header-only path (include/rsk_codec.h): staging
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
-// (rsk_deliver_host) and of the checksum verification (rsk_verify_wire_host).  Pure host code (no HIP
-// calls).
+// (rsk_deliver_host) and of the checksum verification (rsk_verify_wire_host); the single-frame slot
+// staging, the capture filter's text form and the connection keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -184,3 +185,60 @@ extern "C" int rsk_stage_capture_slots(uint32_t n, const uint8_t *arena, const u
     });
     return RSK_OK;
 }
+
+extern "C" {
+
+// The 32-B decode slot of one received frame (EncHead::DecodeBuf reads frame[8] = len; the
+// hashed byte is frame[8 + len] when that lies inside the frame, RConn.cpp:64-75).
+void rsk_stage_decode_header(const uint8_t *frame, int nread, uint8_t *slot) {
+    const int k = nread < 0 ? 0 : (nread < 32 ? nread : 32);
+    std::memcpy(slot, frame, (size_t)k);
+    if (k < 32) std::memset(slot + k, 0, (size_t)(32 - k));
+    if (nread > 8) {
+        const int at = 8 + frame[8];
+        if (at < nread) slot[31] = frame[at];
+    }
+}
+
+// BuildFilterStr (cap/cap_util.cpp:67-144) with proto "tcp" (cap/RCap.cpp:64)
+int rsk_filter_str(const rsk_capture_filter *f, char *buf, size_t buf_len) {
+    if (!f || !buf) return -1;
+    auto ip = [](uint32_t v) {
+        return std::to_string(v & 255u) + "." + std::to_string((v >> 8) & 255u) + "." +
+               std::to_string((v >> 16) & 255u) + "." + std::to_string(v >> 24);
+    };
+    auto ports = [](const rsk_port_list &pl, const char *dir) -> std::string {
+        if (pl.n_single == 0 && pl.n_range == 0) return "";
+        std::string s = "(";
+        for (uint32_t q = 0; q < pl.n_single && q < RSK_FILTER_MAX_PORTS; ++q)
+            s += std::string(" or ") + dir + " port " + std::to_string(pl.single[q]);
+        for (uint32_t q = 0; q < pl.n_range && q < RSK_FILTER_MAX_PORTS; ++q)
+            s += std::string(" or ") + dir + " portrange " + std::to_string(pl.range[q][0]) + "-" +
+                 std::to_string(pl.range[q][1]);
+        s += " )";
+        s.replace(s.find("or"), 2, "");  // the reference removes the first "or"
+        return " and " + s;
+    };
+    std::string out = "tcp";
+    if (f->has_src_ip) out += " and  (ip src " + ip(f->src_ip) + ")";
+    if (f->has_dst_ip) out += " and  (ip dst " + ip(f->dst_ip) + ")";
+    out += ports(f->src_ports, "src");
+    out += ports(f->dst_ports, "dst");
+    if (f->is_server) {
+        std::string s = out;
+        for (size_t pos = s.find("dst"); pos != std::string::npos; pos = s.find("dst")) s.replace(pos, 3, "src");
+        out = "((tcp[tcpflags] & tcp-syn != 0) and " + s + ") or (" + out + "and (tcp[tcpflags] & (tcp-syn) == 0))";
+    }
+    if (out.size() + 1 > buf_len) return -1;
+    std::memcpy(buf, out.c_str(), out.size() + 1);
+    return (int)out.size();
+}
+
+uint64_t rsk_key_for_tcp(uint16_t sp, uint16_t dp) {
+    return 0x10000000ull | ((uint64_t)dp << 16) | (uint64_t)sp;  // KeyGenerator.cpp:16-25
+}
+uint64_t rsk_key_for_udp(uint16_t sp, uint16_t dp) {
+    return 0x20000000ull | ((uint64_t)dp << 16) | (uint64_t)sp;  // KeyGenerator.cpp:27-36
+}
+
+}  // extern "C"

@@ -23,7 +23,8 @@
 //   k_shim          the single-call shims (reference signatures) on a batch of one.
 //   k_tag_table     the key's 256 tags (MD5(key || b)[8..15], b = 0..255), once per context.
 //   k_fill_splitmix synthetic workload generator (bench/tests only).
-// The receive demux is in rsk_demux.hip; host batch helpers in rsk_host.cpp.
+// The receive demux is in rsk_demux.hip; rsk_host.cpp has the host batch helpers and the
+// entry points that need no HIP (rsk_stage_decode_header, rsk_filter_str, rsk_key_for_tcp / _udp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,7 +32,6 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
 #include "../../include/rsk_codec.h"
@@ -243,6 +243,9 @@ __global__ __launch_bounds__(64) void k_enc_sample(const uint16_t *pay_len, uint
     enc_sample(pay_len, n, stat, frame_off, pad);
 }
 
+// Nontemporal loads (bit 0) and stores (bit 1) of the two-pass copies, ld16 / st16's NT (C3 -1.4 % against
+// 2, and 256-thread blocks against 64 / 512 / 1024: profiles/r04r_two_pass_ab.json).
+constexpr int kStream = 3;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <int NT>
 __device__ __forceinline__ uint4 ld16(const uint8_t *p) {
@@ -449,13 +452,13 @@ __device__ __forceinline__ void batch_slots(uint64_t bm, uint32_t lane, uint32_t
     }
 }
 
-template <int PU, int NT, bool TAG, int TG = 0>
+template <int PU, int NT, bool TAG>
 __device__ __forceinline__ void pkt_issue(const EncArgs &a, const Lane1 &L, uint32_t lane, uint64_t bm,
                                           uint4 (&A)[PU][2], uint32_t &b0) {
     uint32_t js[PU], myj;
     bool on[PU], mine;
     batch_slots<PU>(bm, lane, js, on, myj, mine);
-    if constexpr (TAG && TG == 0) {  // payload[0] of the lane's slot packet, ahead of the chunk loads
+    if constexpr (TAG) {  // payload[0] of the lane's slot packet, ahead of the chunk loads
         const uint64_t po = shfl64(L.po, myj);
         b0 = rsk::gptr(a.payload)[mine ? po : 0u];
     }
@@ -502,7 +505,7 @@ __device__ __forceinline__ uint4 merge16(const uint4 &t, const uint4 &v, uint32_
 
 // nxt_bm: the packets of the batch stored after this one (its lowest set bit is the next frame in
 // store order), for the TailCarry hand-over; tc carries a held-back tail chunk between calls.
-template <int PU, int NT, bool TAG, int TG = 0, bool MRG = false>
+template <int PU, int NT, bool TAG, bool MRG = false>
 __device__ __forceinline__ void pkt_store(const EncArgs &a, const KeySched &ks, const Lane1 &L, uint32_t lane,
                                           uint64_t bm, const uint4 (&A)[PU][2], uint32_t my_b0, uint64_t nxt_bm,
                                           TailCarry &tc) {
@@ -510,10 +513,8 @@ __device__ __forceinline__ void pkt_store(const EncArgs &a, const KeySched &ks, 
     bool on[PU], mine;
     batch_slots<PU>(bm, lane, js, on, myj, mine);
     uint32_t t0 = 0, t1 = 0;
-    if constexpr (TAG && TG == 0) {
+    if constexpr (TAG) {
         tag_of(ks, my_b0, t0, t1);
-    } else if constexpr (TAG) {
-        // the tag prepass (copy_pkt_pipe) left each packet's tag and payload[0] in its own lane's H
     } else {  // lane p: the header chunks of its slot packet (store_head)
         uint32_t H[8];
 #pragma unroll
@@ -543,14 +544,9 @@ __device__ __forceinline__ void pkt_store(const EncArgs &a, const KeySched &ks, 
         if constexpr (TAG) {
 #pragma unroll
             for (int t = 2; t < 8; ++t) Hj[t] = rdl(L.H[t], js[p]);
-            if constexpr (TG == 0) {
-                Hj[0] = rdl(t0, (uint32_t)p);
-                Hj[1] = rdl(t1, (uint32_t)p);
-                Hj[7] |= rdl(my_b0, (uint32_t)p) << 24;
-            } else {
-                Hj[0] = rdl(L.H[0], js[p]);
-                Hj[1] = rdl(L.H[1], js[p]);
-            }
+            Hj[0] = rdl(t0, (uint32_t)p);
+            Hj[1] = rdl(t1, (uint32_t)p);
+            Hj[7] |= rdl(my_b0, (uint32_t)p) << 24;
             if constexpr (MRG) {
                 // byte-packed neighbours (no padding): this frame's first chunk completes the held-back
                 // tail of the previous frame; its own last chunk is held back when the next frame in
@@ -598,31 +594,10 @@ __device__ __forceinline__ void pkt_store(const EncArgs &a, const KeySched &ks, 
     }
 }
 
-// Tag prepass (TAG form, TG > 0): before the batch that needs them, the lanes of the next TG packets
-// (in copy order) load their payload[0] and run their MD5 together, one compression pass per TG
-// packets instead of one per batch of PU packets (a pass costs the same VALU issue however few lanes
-// are active); the byte loads fetch each payload's first line at most TG / PU batches before its
-// chunk loads.  TG == 0: payload[0] loaded beside the batch's chunk loads, MD5 per batch (round 2).
-template <int TG>
-__device__ __forceinline__ void tag_prepass(const EncArgs &a, const KeySched &ks, Lane1 &L, uint32_t lane,
-                                            uint64_t bm, uint64_t &untagged) {
-    if constexpr (TG > 0) {
-        if (!(bm & untagged)) return;  // uniform
-        uint64_t m = 0;
-#pragma unroll
-        for (int k = 0; k < TG; ++k) {
-            const uint64_t b = untagged & (~untagged + 1ull);
-            m |= b;
-            untagged ^= b;
-        }
-        if ((m >> lane) & 1ull) encode_tag(a, ks, L);
-    }
-}
-
 // MRG: the TailCarry hand-over between byte-packed neighbours (sets with an unaligned frame end and
 // no padding only: the carried chunk costs SGPRs the other sets spend on the pipelined copy).
-template <int PU, int NT, bool TAG, int TG = 0, bool MRG = false>
-__device__ __forceinline__ void copy_pkt_pipe(const EncArgs &a, const KeySched &ks, Lane1 &L, uint32_t lane,
+template <int PU, int NT, bool TAG, bool MRG = false>
+__device__ __forceinline__ void copy_pkt_pipe(const EncArgs &a, const KeySched &ks, const Lane1 &L, uint32_t lane,
                                               uint64_t vm) {
     uint4 A0[PU][2], A1[PU][2];
     uint32_t b0a = 0, b0b = 0;
@@ -630,20 +605,17 @@ __device__ __forceinline__ void copy_pkt_pipe(const EncArgs &a, const KeySched &
     tc.t = make_uint4(0u, 0u, 0u, 0u);
     tc.at = 0;
     tc.on = false;
-    uint64_t untagged = TAG ? vm : 0ull;
     uint64_t cur = take_batch<PU>(vm);
     if (!cur) return;
-    pkt_issue<PU, NT, TAG, TG>(a, L, lane, cur, A0, b0a);
+    pkt_issue<PU, NT, TAG>(a, L, lane, cur, A0, b0a);
     while (true) {
         const uint64_t nxt = take_batch<PU>(vm);
-        if (nxt) pkt_issue<PU, NT, TAG, TG>(a, L, lane, nxt, A1, b0b);
-        if constexpr (TAG) tag_prepass<TG>(a, ks, L, lane, cur, untagged);
-        pkt_store<PU, NT, TAG, TG, MRG>(a, ks, L, lane, cur, A0, b0a, nxt, tc);
+        if (nxt) pkt_issue<PU, NT, TAG>(a, L, lane, nxt, A1, b0b);
+        pkt_store<PU, NT, TAG, MRG>(a, ks, L, lane, cur, A0, b0a, nxt, tc);
         if (!nxt) break;
         cur = take_batch<PU>(vm);
-        if (cur) pkt_issue<PU, NT, TAG, TG>(a, L, lane, cur, A0, b0a);
-        if constexpr (TAG) tag_prepass<TG>(a, ks, L, lane, nxt, untagged);
-        pkt_store<PU, NT, TAG, TG, MRG>(a, ks, L, lane, nxt, A1, b0b, cur, tc);
+        if (cur) pkt_issue<PU, NT, TAG>(a, L, lane, cur, A0, b0a);
+        pkt_store<PU, NT, TAG, MRG>(a, ks, L, lane, nxt, A1, b0b, cur, tc);
         if (!cur) break;
     }
 }
@@ -652,25 +624,23 @@ __device__ __forceinline__ void copy_pkt_pipe(const EncArgs &a, const KeySched &
 // lane l of iteration t takes chunk g = 64(U t + u) + l and finds its packet by a 6-step binary
 // search over the set's prefix sums in this wave's LDS slice.  Wave-local: no block barrier, so
 // waves of one block may take different copy paths.
-// TAGQ: phase 1 left the tag; `payload[0]` is loaded right after the first iteration's chunk loads
+// Phase 1 left the tag; `payload[0]` is loaded right after the first iteration's chunk loads
 // (both depend only on the descriptors) and the packet's lane then stores its header chunks, so
-// the set pays one dependent global round trip less than with the tag before the copy.
-template <int U, bool TAGQ = false, bool LANE = false>
+// the set pays one dependent global round trip less than with the tag before the copy.  The tag on
+// the generic MD5 schedule: see the measurements at tag_of.
 __device__ __forceinline__ void flat_head(const EncArgs &a, const KeySched &ks, const Lane1 &L, bool mine) {
-    if constexpr (TAGQ) {
-        if (mine) {
-            const uint32_t b0 = rsk::gptr(a.payload)[L.po];
-            uint32_t H[8];
+    if (mine) {
+        const uint32_t b0 = rsk::gptr(a.payload)[L.po];
+        uint32_t H[8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) H[q] = L.H[q];
-            tag_of<LANE>(ks, b0, H[0], H[1]);
-            H[7] |= b0 << 24;
-            store_head(H, a.frame + L.fo);
-        }
+        for (int q = 0; q < 8; ++q) H[q] = L.H[q];
+        tag_of(ks, b0, H[0], H[1]);
+        H[7] |= b0 << 24;
+        store_head(H, a.frame + L.fo);
     }
 }
 
-template <int U, bool TAGQ = false, bool LANE = false>
+template <int U>
 __device__ __forceinline__ void copy_flat(const EncArgs &a, const KeySched &ks, const Lane1 &L, uint32_t lane,
                                           bool mine, CopyRec *recs, uint32_t *cend) {
     uint32_t cc = 0;
@@ -730,13 +700,49 @@ __device__ __forceinline__ void copy_flat(const EncArgs &a, const KeySched &ks, 
                 lims[u] = (int32_t)rr.flen - 32 - 16 * m;
             }
         }
-        if (TAGQ && g0 == 0u) flat_head<U, TAGQ, LANE>(a, ks, L, mine);
+        if (g0 == 0u) flat_head(a, ks, L, mine);
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (act[u]) store_piece<0>(dsts[u], funnel16_lane(A[u], B[u], shs[u]), los[u], lims[u], a.pad != 0u);
     }
-    if (TAGQ && C == 0u) flat_head<U, TAGQ, LANE>(a, ks, L, mine);
+    if (C == 0u) flat_head(a, ks, L, mine);
     wave_lds_sync();  // LDS slice reusable by the caller afterwards
+}
+
+// ---- the per-set kernels (k_encode, k_encode_wire): packet mapping and store policy ---------------
+// Grouped-interleave mapping.  A super-block of kSetSbw consecutive waves owns kSetSbw * 64
+// consecutive packets; wave wl of it takes groups of kSetGrp consecutive packets strided by
+// kSetSbw * kSetGrp (lane l: group (l / kSetGrp) * kSetSbw + wl, packet l % kSetGrp in it).  Each wave
+// still frames 64 packets (descriptor loads coalesced per 8-packet group), but the resident waves copy
+// one compact stretch of the arenas at a time (kSetSbw * kSetGrp packets per super-block) instead of
+// each its own region 64 packets from the next wave's: C3 -3.7 %, C4 -4.1 %, C2 within 1 % against the
+// tiled mapping (profiles/r02_ab_encode_mapping.json; renumbering the blocks so that each XCD's blocks
+// own consecutive waves measured no gain, profiles/r01_ab_xcd_map.json).  The grid holds only waves
+// that own a packet (enc_grid).
+constexpr uint32_t kSetGrp = 8, kSetSbw = 1024;
+
+// The packet of lane `lane` of the grid's wave wg (n: past the batch); false (wave-uniform) when the
+// wave owns no packet.
+__device__ __forceinline__ bool set_packet(uint64_t wg, uint32_t lane, uint32_t n, uint64_t &i) {
+    const uint64_t sb = wg / kSetSbw, wl = wg % kSetSbw;
+    if (sb * kSetSbw * 64u + wl * kSetGrp >= n) return false;  // the wave's smallest packet
+    const uint64_t gi = sb * kSetSbw * 64u + ((uint64_t)(lane / kSetGrp) * kSetSbw + wl) * kSetGrp + lane % kSetGrp;
+    i = gi < n ? gi : n;
+    return true;
+}
+
+// The set's frames (or wire packets: `len` bytes at frame + fo; on: the lane's is written) leave gaps:
+// some pair of neighbours in one group (the last packet of a group: the next lane's packet is not the
+// next frame) does not lie back to back, padded end to start.  nfo / non: the next lane's offset, and
+// whether it is written.
+__device__ __forceinline__ bool set_gaps(const EncArgs &a, uint64_t fo, uint32_t len, bool on, uint32_t lane,
+                                         uint64_t &nfo, bool &non) {
+    const uint32_t fend = on ? padded_len(a.frame + fo, len, a.pad) : 0u;
+    const uint64_t end = fo + fend;
+    nfo = (uint64_t)(uint32_t)__shfl_down((int)(uint32_t)fo, 1) |
+          ((uint64_t)(uint32_t)__shfl_down((int)(uint32_t)(fo >> 32), 1) << 32);
+    non = __shfl_down((int)on, 1) != 0;
+    return __ballot(on && non && lane % kSetGrp != kSetGrp - 1u && end != nfo) != 0ull;
 }
 
 // Copy-path choice for the hybrid kernel: the per-packet loop wastes lanes on short frames (a
@@ -753,7 +759,7 @@ constexpr uint32_t kDeferTagMeanBytes = 1024;
 // deferred into the copy loop for sets of long frames; MODE 19 (the short path): every set on the
 // flat list, for batches of short frames only (the per-packet copy's registers out of the kernel).
 // The store policy is chosen per set (below).
-template <int MODE, int PU, int U, int GRP = 64, int TG = 0>
+template <int MODE, int PU, int U>
 __device__ __forceinline__ void encode_set(const EncArgs &a, const KeySched &ks, uint64_t i, uint32_t lane,
                                            CopyRec *recs, uint32_t *cend) {
     static_assert(MODE == 11 || MODE == 19, "the per-set kernel and its flat-only build");
@@ -769,7 +775,7 @@ __device__ __forceinline__ void encode_set(const EncArgs &a, const KeySched &ks,
     const bool defer = !flat && fl >= kDeferTagMeanBytes * cnt;
     if (!defer && !flat) encode_tag(a, ks, L);  // the flat list and the deferred copy take it themselves
     if (flat) {
-        copy_flat<U, true, false>(a, ks, L, lane, vec, recs, cend);
+        copy_flat<U>(a, ks, L, lane, vec, recs, cend);
         return;
     }
     if constexpr (MODE == 11) {
@@ -777,13 +783,9 @@ __device__ __forceinline__ void encode_set(const EncArgs &a, const KeySched &ks,
         // frame's start, so every line of the span is written in full) keep normal stores; any gap
         // leaves partially written lines, which nontemporal stores write without the memory-side
         // read-modify-write (C4's 1440-B slots: -13 %; C3's packed frames: +4 % if streamed).
-        const uint32_t fend = vec ? padded_len(a.frame + L.fo, (uint32_t)L.st, a.pad) : 0u;
-        const uint64_t end = L.fo + fend;
-        const uint64_t nfo = (uint64_t)(uint32_t)__shfl_down((int)(uint32_t)L.fo, 1) |
-                             ((uint64_t)(uint32_t)__shfl_down((int)(uint32_t)(L.fo >> 32), 1) << 32);
-        const bool nvec = __shfl_down((int)vec, 1) != 0;
-        // (lanes of the last packet of a group: the next lane's packet is not the next frame)
-        const bool nt = __ballot(vec && nvec && lane % GRP != GRP - 1u && end != nfo) != 0ull;
+        uint64_t nfo;
+        bool nvec;
+        const bool nt = set_gaps(a, L.fo, (uint32_t)L.st, vec, lane, nfo, nvec);
         // Header chunks: sets with the tag in the copy loop (long frames) store them in the packet's
         // first slot store (lanes 0..2, words by readlane); the others by the slot lane (store_head).
         // Measured (profiles/r02_ab_head.json): C3 2.34 vs 2.55 ms with the first; C4 0.389 vs
@@ -793,18 +795,18 @@ __device__ __forceinline__ void encode_set(const EncArgs &a, const KeySched &ks,
         // each shared chunk as one 16-B store.  Only sets that really have such a pair take it: the
         // carry costs ~8 % where nothing merges (C3 frames at odd offsets 0.769 -> 0.704 ms, C3
         // slots without padding 0.682 -> 0.630 ms, gpurun_out/r03lay).  Short-frame sets keep
-        // their copy: the TAG form with the tag from phase 1 (TG = -1) was slower on C4's
-        // byte-packed frames (0.486 vs 0.466 ms).
+        // their copy: the TAG form with the tag from phase 1 was slower on C4's byte-packed frames
+        // (0.486 vs 0.466 ms).
         bool mrg = false;
         if (a.pad == 0u && defer) {
             const uint64_t fe = reinterpret_cast<uintptr_t>(a.frame + L.fo) + (uint32_t)L.st;
-            mrg = __ballot(vec && nvec && lane % GRP != GRP - 1u && (fe & 15u) != 0u &&
+            mrg = __ballot(vec && nvec && lane % kSetGrp != kSetGrp - 1u && (fe & 15u) != 0u &&
                            reinterpret_cast<uintptr_t>(a.frame + nfo) == fe) != 0ull;
         }
         if (defer) {
-            if (mrg) copy_pkt_pipe<PU, 0, true, TG, true>(a, ks, L, lane, vm);
-            else if (nt) copy_pkt_pipe<PU, 2, true, TG>(a, ks, L, lane, vm);
-            else copy_pkt_pipe<PU, 0, true, TG>(a, ks, L, lane, vm);
+            if (mrg) copy_pkt_pipe<PU, 0, true, true>(a, ks, L, lane, vm);
+            else if (nt) copy_pkt_pipe<PU, 2, true>(a, ks, L, lane, vm);
+            else copy_pkt_pipe<PU, 0, true>(a, ks, L, lane, vm);
         } else {
             if (nt) copy_pkt_pipe<PU, 2, false>(a, ks, L, lane, vm);
             else copy_pkt_pipe<PU, 0, false>(a, ks, L, lane, vm);
@@ -827,13 +829,12 @@ __device__ __forceinline__ void encode_set(const EncArgs &a, const KeySched &ks,
 // Records chunk-major (round 6): chunk 0 of packet i at heads[i], chunk 1 at heads[nr + i] (nr = the
 // records' capacity in packets), so each store instruction of a wave writes 1 KB contiguous instead of
 // 16-B pieces at a 32-B stride.
-template <int SADD = 0>
 __global__ __launch_bounds__(kBlock) void k_encode_heads(EncArgs a, KeySched ks, uint4 *heads, uint32_t *stat,
                                                          uint64_t base, uint64_t nr) {
     stage_tags(ks);
     enc_sample(a.pay_len, a.n, stat, a.frame_off, a.pad);
     const uint64_t i = base + (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const Lane1 L = encode_phase1<true, true, SADD>(a, ks, i < a.n ? i : a.n);
+    const Lane1 L = encode_phase1<true, true>(a, ks, i < a.n ? i : a.n);
     if (i < a.n && L.st > 0) {
         heads[i] = make_uint4(L.H[0], L.H[1], L.H[2], L.H[3]);
         heads[nr + i] = make_uint4(L.H[4], L.H[5], L.H[6], L.H[7]);
@@ -855,7 +856,7 @@ struct CopyK {
     uint32_t flen[K];  // frame bytes counted from g.d0 (31 + P + r); 0: packet not framed
 };
 
-template <int K, int NT>
+template <int K>
 __device__ __forceinline__ void copyk_issue(const EncArgs &a, uint64_t i0, uint32_t lane, CopyK<K> &c) {
     uint32_t dP = 0;
     uint64_t dpo = 0, dfo = 0;
@@ -904,13 +905,13 @@ __device__ __forceinline__ void copyk_issue(const EncArgs &a, uint64_t i0, uint3
             if (!on || m_hi < m_lo || (q == 1 && c.g[p].nst < 64u)) continue;  // uniform
             const int32_t m = (int32_t)(lane + 64u * q) - 2;
             const int32_t mc = m < m_lo ? m_lo : m > m_hi ? m_hi : m;
-            c.A[p][q] = ld16<NT>(c.g[p].srcp + 16 * mc);  // uniform base + lane offset
+            c.A[p][q] = ld16<kStream>(c.g[p].srcp + 16 * mc);  // uniform base + lane offset
         }
     }
 }
 
 // Store packet p's chunks, the header chunks from the packet's 8 header words Hj (its pass-1 record).
-template <int K, int NT>
+template <int K>
 __device__ __forceinline__ void copyk_store(const EncArgs &a, const CopyK<K> &c, int p, uint32_t lane,
                                             const uint32_t (&Hj)[8]) {
     const FrameGeo &g = c.g[p];
@@ -932,32 +933,31 @@ __device__ __forceinline__ void copyk_store(const EncArgs &a, const CopyK<K> &c,
         const uint4 V = rsk::funnel16(c.A[p][q], B[q], g.sh);
         const uint4 v = k < (g.r >= 2u ? 3u : 2u) ? head_chunk(Hj, k, g.r, V) : V;
         if (k >= nst) continue;
-        store_piece<NT>(g.d0 + 16u * k, v, k == 0u ? g.r : 0u, (int)fl - 16 * (int)k, a.pad != 0u);
+        store_piece<kStream>(g.d0 + 16u * k, v, k == 0u ? g.r : 0u, (int)fl - 16 * (int)k, a.pad != 0u);
     }
 }
 
-// NT: bit 0 nontemporal loads, bit 1 nontemporal stores (shipped: 3; C3 -1.4 % against 2, and 256-thread
-// blocks against 64 / 512 / 1024: profiles/r04r_two_pass_ab.json).  K: packets per wave (round 5):
+// Nontemporal loads and stores (kStream).  K: packets per wave (round 5):
 // every chunk load of the K packets is issued before any store, so a wave carries K frames' bytes in
 // flight -- the chip retires a bounded number of waves per second (the one-packet waves of C3 run at
 // ~2 G waves/s), so short frames need several per wave to keep the memory system busy.
 // base: the launch's first packet (a grid is limited to 2^32 - 1 work-items, i.e. 2^26 packets at 64
 // per packet: larger batches take several launches, kCopyMaxPackets each).
-template <int NT, int K = 1>
+template <int K>
 __global__ __launch_bounds__(kBlock) void k_encode_copy(EncArgs a, const uint32_t *heads, uint64_t base, uint64_t nr) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t i0 = base + ((uint64_t)blockIdx.x * kWavesPerBlock + w) * K;
     if (i0 >= a.n) return;
     CopyK<K> c;
-    copyk_issue<K, NT>(a, i0, lane, c);
+    copyk_issue<K>(a, i0, lane, c);
 #pragma unroll
     for (int p = 0; p < K; ++p) {
         if (!c.flen[p]) continue;  // uniform
         uint32_t Hj[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) Hj[t] = heads[4 * ((t < 4 ? 0 : nr) + i0 + p) + (t & 3)];  // uniform: scalar loads
-        copyk_store<K, NT>(a, c, p, lane, Hj);
+        copyk_store<K>(a, c, p, lane, Hj);
     }
 }
 
@@ -973,7 +973,7 @@ __global__ __launch_bounds__(kBlock) void k_encode_copy(EncArgs a, const uint32_
 // every chunk a frame touches is written once, whole, unless it also holds bytes outside every frame.
 // The header pass (k_encode_heads_os) maps each block to the first packet that can reach it and
 // checks that the frames are laid out in packet order without overlap; otherwise (or when the gaps
-// are wide) k_encode_os copies packet by packet as k_encode_copy<NT, 1> does.
+// are wide) k_encode_os copies packet by packet as k_encode_copy<1> does.
 constexpr uint32_t kOsBlock = 2048;  // bytes per wave-iteration: 2 chunks per lane (1 KB: 0.487 ms on C4 byte-packed; 4 KB: 141 VGPRs)
 constexpr uint32_t kOsMaxGapBlocks = 16;  // blocks one packet may map (wider gaps: the fallback)
 struct OsMap {
@@ -985,13 +985,12 @@ __device__ __forceinline__ uint32_t os_ext(const EncArgs &a, uint64_t fo, uint32
     return P != 0u && P <= (uint32_t)RSK_MAX_PAYLOAD ? padded_len(a.frame + fo, RSK_HEAD_SIZE + P, a.pad) : 0u;
 }
 
-template <int SADD = 0>
 __global__ __launch_bounds__(kBlock) void k_encode_heads_os(EncArgs a, KeySched ks, uint4 *heads, uint32_t *stat,
                                                             uint64_t nr, OsMap m) {
     stage_tags(ks);
     enc_sample(a.pay_len, a.n, stat, a.frame_off, a.pad);
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const Lane1 L = encode_phase1<true, true, SADD>(a, ks, i < a.n ? i : a.n);
+    const Lane1 L = encode_phase1<true, true>(a, ks, i < a.n ? i : a.n);
     bool bad = false;
     if (i < a.n) {
         if (L.st > 0) {
@@ -1036,7 +1035,6 @@ struct OsLd {
     uint4 A, B, H0, H1;
     uint32_t sh;
 };
-template <int NT>
 __device__ __forceinline__ OsLd os_load(const EncArgs &a, const uint4 *heads, uint64_t nr, const OsFrame &F,
                                         uint32_t t) {
     OsLd L;
@@ -1047,8 +1045,8 @@ __device__ __forceinline__ OsLd os_load(const EncArgs &a, const uint4 *heads, ui
     const int64_t c1 = (int64_t)c0 + 16;  // chunks outside the payload: any payload chunk (masked)
     const uint64_t a0 = (int64_t)c0 < (int64_t)lo ? lo : c0 > hi ? hi : c0;
     const uint64_t a1 = c1 < (int64_t)lo ? lo : (uint64_t)c1 > hi ? hi : (uint64_t)c1;
-    L.A = ld16<NT & 1>(a.payload + a0);
-    L.B = ld16<NT & 1>(a.payload + a1);
+    L.A = ld16<kStream>(a.payload + a0);
+    L.B = ld16<kStream>(a.payload + a1);
     L.H0 = heads[F.p];
     L.H1 = heads[nr + F.p];
     return L;
@@ -1099,7 +1097,6 @@ __device__ __forceinline__ OsWin os_window(const EncArgs &a, uint32_t p0, uint32
 // then) and F2 = the first framed packet starting inside the chunk; the loop over the block's packets
 // only counts (32-bit starts relative to B0), the frames' fields come from their window lanes by one
 // ds_bpermute each (round 6: selecting whole frame records in the loop cost ~200 VALU per block).
-template <int NT>
 __device__ __forceinline__ void os_block(const EncArgs &a, const uint4 *heads, uint64_t nr, const OsWin &W,
                                          uint32_t jlo, uint32_t jhi, uint64_t B0, uint32_t lane) {
     constexpr int U = kOsBlock / 1024;  // chunks per lane, 1 KB apart
@@ -1146,7 +1143,7 @@ __device__ __forceinline__ void os_block(const EncArgs &a, const uint4 *heads, u
         }
         F1[u].p = W.p0 + k1;
         p2[u] = W.p0 + k2;
-        L[u] = os_load<NT>(a, heads, nr, F1[u], t1[u]);
+        L[u] = os_load(a, heads, nr, F1[u], t1[u]);
         G[u] = heads[p2[u] < a.n ? p2[u] : 0u];
     }
     uint4 v[U];
@@ -1164,7 +1161,7 @@ __device__ __forceinline__ void os_block(const EncArgs &a, const uint4 *heads, u
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         uint8_t *d = reinterpret_cast<uint8_t *>(B0 + 1024u * u + 16u * lane);
-        if (c1[u] == 16u || (uu[u] < 16u && c1[u] == uu[u])) st16<NT>(d, v[u]);  // the whole chunk is frame bytes
+        if (c1[u] == 16u || (uu[u] < 16u && c1[u] == uu[u])) st16<kStream>(d, v[u]);  // the whole chunk is frame bytes
         else {
             if (c1[u]) rsk::store_range16(d, v[u], 0u, c1[u]);
             if (uu[u] < 16u) rsk::store_range16(d, v[u], uu[u], 16u);
@@ -1175,7 +1172,6 @@ __device__ __forceinline__ void os_block(const EncArgs &a, const uint4 *heads, u
 // Persistent waves, each streaming its own contiguous range of blocks with a sliding window of 64
 // packets' descriptors (one block-map load per wave, one descriptor load per 64 packets), or, when the
 // header pass flagged the layout, copying packet by packet.
-template <int NT>
 __global__ __launch_bounds__(kBlock) void k_encode_os(EncArgs a, const uint4 *heads, uint64_t nr, const uint32_t *bfirst,
                                                       const uint32_t *ctl, uint32_t epoch) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -1183,14 +1179,14 @@ __global__ __launch_bounds__(kBlock) void k_encode_os(EncArgs a, const uint4 *he
     const uint64_t wid = (uint64_t)blockIdx.x * kWavesPerBlock + w, nw = (uint64_t)gridDim.x * kWavesPerBlock;
     if (__hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) {
         const uint32_t *hr = reinterpret_cast<const uint32_t *>(heads);
-        for (uint64_t i0 = wid; i0 < a.n; i0 += nw) {  // packet by packet (k_encode_copy<NT, 1>)
+        for (uint64_t i0 = wid; i0 < a.n; i0 += nw) {  // packet by packet (k_encode_copy<1>)
             CopyK<1> c;
-            copyk_issue<1, NT>(a, i0, lane, c);
+            copyk_issue<1>(a, i0, lane, c);
             if (!c.flen[0]) continue;  // uniform
             uint32_t Hj[8];
 #pragma unroll
             for (int t = 0; t < 8; ++t) Hj[t] = hr[4 * ((t < 4 ? 0 : nr) + i0) + (t & 3)];
-            copyk_store<1, NT>(a, c, 0, lane, Hj);
+            copyk_store<1>(a, c, 0, lane, Hj);
         }
         return;
     }
@@ -1209,14 +1205,14 @@ __global__ __launch_bounds__(kBlock) void k_encode_os(EncArgs a, const uint4 *he
             if (past != 0ull || (W.p0 + 64ull >= a.n)) {
                 const uint32_t jlo = live ? (uint32_t)__builtin_ctzll(live) : 64u;
                 const uint32_t jhi = past ? (uint32_t)__builtin_ctzll(past) : 64u;  // first starting past
-                if (jlo < jhi) os_block<NT>(a, heads, nr, W, jlo, jhi - 1u, B0, lane);
+                if (jlo < jhi) os_block(a, heads, nr, W, jlo, jhi - 1u, B0, lane);
                 break;
             }
             // every packet of the window starts inside or before the block: move on by the packets
             // that end before it (at least one, else the whole window is inside the block: by 32)
             const uint32_t adv = live ? (uint32_t)__builtin_ctzll(live) : 64u;
             if (adv == 0u) {  // a block holding 64 packet starts (tiny or dropped packets): by halves
-                os_block<NT>(a, heads, nr, W, 0u, 31u, B0, lane);  // packets 0..31, then from 32 on
+                os_block(a, heads, nr, W, 0u, 31u, B0, lane);  // packets 0..31, then from 32 on
                 W = os_window(a, W.p0 + 32u, lane);
                 continue;
             }
@@ -1225,27 +1221,16 @@ __global__ __launch_bounds__(kBlock) void k_encode_os(EncArgs a, const uint4 *he
     }
 }
 
-// Grouped-interleave mapping (shipped: GRP 8, SBW 1024).  A super-block of SBW consecutive waves owns
-// SBW * 64 consecutive packets; wave wl of it takes groups of GRP consecutive packets strided by
-// SBW * GRP (lane l: group (l / GRP) * SBW + wl, packet l % GRP in it).  Each wave still frames 64
-// packets (descriptor loads coalesced per 8-packet group), but the resident waves copy one compact
-// stretch of the arenas at a time (SBW * GRP packets per super-block) instead of each its own region
-// 64 packets from the next wave's: C3 -3.7 %, C4 -4.1 %, C2 within 1 % against the tiled mapping
-// (profiles/r02_ab_encode_mapping.json; renumbering the blocks so that each XCD's blocks own
-// consecutive waves measured no gain, profiles/r01_ab_xcd_map.json).  The grid holds only waves
-// that own a packet (enc_grid).
-template <int MODE, int PU, int U, int GRP, int SBW, int TG = 0>
+// One set per wave on the grouped-interleave mapping (set_packet; grid: enc_grid).
+template <int MODE, int PU, int U>
 __global__ __launch_bounds__(kBlock) void k_encode(EncArgs a, KeySched ks) {
     __shared__ CopyRec recs[kWavesPerBlock][64];
     __shared__ uint32_t cend[kWavesPerBlock][64];
     stage_tags(ks);
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t wg = (uint64_t)blockIdx.x * kWavesPerBlock + w;
-    const uint64_t sb = wg / SBW, wl = wg % SBW;
-    const uint64_t first = sb * SBW * 64u + wl * GRP;  // the wave's smallest packet
-    if (first >= a.n) return;  // wave-uniform
-    const uint64_t i = sb * SBW * 64u + ((uint64_t)(lane / GRP) * SBW + wl) * GRP + lane % GRP;
-    encode_set<MODE, PU, U, GRP, TG>(a, ks, i < a.n ? i : a.n, lane, recs[w], cend[w]);
+    uint64_t i;
+    if (!set_packet((uint64_t)blockIdx.x * kWavesPerBlock + w, lane, a.n, i)) return;  // wave-uniform
+    encode_set<MODE, PU, U>(a, ks, i, lane, recs[w], cend[w]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1799,7 +1784,6 @@ struct WireLds {
 };
 
 // Per-wave copy-path choice (identical in both launches).
-template <int E>
 __device__ __forceinline__ bool wire_flat_choice(bool vec, uint32_t wlen) {
     uint32_t fl = vec ? wlen : 0u;
 #pragma unroll
@@ -1813,12 +1797,12 @@ __device__ __forceinline__ void encode_wire_set(const EncArgs &a, const WireArgs
     using G = WireGeom<E>;
     __shared__ uint4 lds[kWavesPerBlock][WireLds<E, MODE>::kBytes / 16];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    // set_packet's mapping, spelled out: through the helper these kernels' register allocation changes
     const uint64_t wg = (uint64_t)blockIdx.x * kWavesPerBlock + w;
-    constexpr uint32_t kGrp = 8u;
-    const uint64_t sb = wg / 1024u, wl = wg % 1024u;
-    const uint64_t first = sb * 65536u + wl * 8u;
+    const uint64_t sb = wg / kSetSbw, wl = wg % kSetSbw;
+    const uint64_t first = sb * (kSetSbw * 64u) + wl * kSetGrp;
     if (first >= a.n) return;  // wave-uniform; no block barriers below
-    const uint64_t gi = sb * 65536u + ((uint64_t)(lane / 8u) * 1024u + wl) * 8u + lane % 8u;
+    const uint64_t gi = sb * (kSetSbw * 64u) + ((uint64_t)(lane / kSetGrp) * kSetSbw + wl) * kSetGrp + lane % kSetGrp;
     const uint64_t i = gi < a.n ? gi : a.n;
     {  // is this set ours?
         bool v0 = false;
@@ -1828,7 +1812,7 @@ __device__ __forceinline__ void encode_wire_set(const EncArgs &a, const WireArgs
             v0 = P != 0u && P <= (uint32_t)RSK_MAX_PAYLOAD;  // any alignment: both copies take all
             wlen = G::HL + RSK_HEAD_SIZE + P;
         }
-        if (wire_flat_choice<E>(v0, wlen) != (MODE == 4)) return;
+        if (wire_flat_choice(v0, wlen) != (MODE == 4)) return;
     }
     Lane1 L = encode_phase1<MODE != 5>(a, ks, i);
     bool defer = false;
@@ -1864,12 +1848,9 @@ __device__ __forceinline__ void encode_wire_set(const EncArgs &a, const WireArgs
     } else {
         wave_lds_sync();
         // store policy per set, as k_encode: stream the stores when the wire packets leave gaps
-        const uint32_t wend = vec ? padded_len(a.frame + L.fo, (uint32_t)wst, a.pad) : 0u;
-        const uint64_t end = L.fo + wend;
-        const uint64_t nfo = (uint64_t)(uint32_t)__shfl_down((int)(uint32_t)L.fo, 1) |
-                             ((uint64_t)(uint32_t)__shfl_down((int)(uint32_t)(L.fo >> 32), 1) << 32);
-        const bool nvec = __shfl_down((int)vec, 1) != 0;
-        const bool gaps = __ballot(vec && nvec && lane % kGrp != kGrp - 1u && end != nfo) != 0ull;
+        uint64_t nfo;
+        bool nvec;
+        const bool gaps = set_gaps(a, L.fo, (uint32_t)wst, vec, lane, nfo, nvec);
         if (defer) {
             if (gaps) copy_wire_pkt_dpp<E, PU, 2, true>(a, ks, L, stage, sum_pre, wst, lane, vm);
             else copy_wire_pkt_dpp<E, PU, 0, true>(a, ks, L, stage, sum_pre, wst, lane, vm);
@@ -1966,7 +1947,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_heads(EncArgs a, WireArgs wa, K
 }
 
 // base: the launch's first packet; rbase / stride: the record chunk's (k_wire_heads)
-template <int E, int NT, int K>
+template <int E, int K>
 __global__ __launch_bounds__(kBlock) void k_wire_copy(EncArgs a, const uint4 *rec, uint64_t base, uint64_t rbase,
                                                       uint64_t stride) {
     using G = WireGeom<E>;
@@ -2008,7 +1989,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_copy(EncArgs a, const uint4 *re
             if (!on || (q == 1 && nch < 64u)) continue;  // uniform
             const int32_t m = (int32_t)(lane + 64u * q) - Q;
             const int32_t mc = m < m_lo ? m_lo : m > m_hi ? m_hi : m;  // dead lanes re-read a live chunk
-            A[p][q] = ld16<NT>(srcp + 16 * mc);
+            A[p][q] = ld16<kStream>(srcp + 16 * mc);
         }
     }
     // Three phases over the K packets, so the packets' dependency chains overlap (round 6: one packet at a
@@ -2077,7 +2058,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_copy(EncArgs a, const uint4 *re
             for (int q = 0; q < 2; ++q) {
                 const uint32_t k = lane + 64u * q;
                 if (q == 1 && nst <= 64u) continue;  // uniform
-                if (k < nst) store_last16<NT>(d0 + 16u * k, VI[p][q], (int)wlen - 16 * (int)k, pad);
+                if (k < nst) store_last16<kStream>(d0 + 16u * k, VI[p][q], (int)wlen - 16 * (int)k, pad);
             }
         } else {
             const uint4 l63 = rdl4(VI[p][0], 63);
@@ -2091,7 +2072,7 @@ __global__ __launch_bounds__(kBlock) void k_wire_copy(EncArgs a, const uint4 *re
                 const uint32_t j = lane + 64u * q;
                 if (j >= nst) continue;
                 if (j == 0u) rsk::store_range16(d0, d, r, 16u);
-                else store_last16<NT>(d0 + 16u * j, d, (int)(r + wlen) - 16 * (int)j, pad);
+                else store_last16<kStream>(d0 + 16u * j, d, (int)(r + wlen) - 16 * (int)j, pad);
             }
         }
     }
@@ -2960,10 +2941,24 @@ int ensure_compact(rsk_ctx *c, uint32_t n, hipStream_t s, Compact &k) {
     return RSK_OK;
 }
 
-int run_compaction(rsk_ctx *c, const Compact &k, uint32_t *valid_idx, uint32_t *n_valid, hipStream_t s) {
+// A decode-family launch, with the compaction behind it when the caller asked for the index list or
+// the count: launch(masks) starts the kernel `what` on st with the per-wave ballot workspace (null:
+// no compaction).
+template <class F>
+int launch_compacted(rsk_ctx *c, uint32_t n, uint32_t *idx, uint32_t *count, hipStream_t st, const char *what,
+                     F launch) {
+    const bool compact = idx || count;
+    Compact k;
+    if (compact) {
+        int r = ensure_compact(c, n, st, k);
+        if (r) return r;
+    }
+    launch(k.masks);
+    int r = launch_check(what);
+    if (r || !compact) return r;
     const uint32_t stall = c->compact_stall_tile.exchange(~0u, std::memory_order_relaxed);
-    hipLaunchKernelGGL(k_compact, dim3(k.ntiles), dim3(kBlock), 0, s, k.masks, k.nw, k.st, valid_idx, n_valid,
-                       c->err_dev, stall);
+    hipLaunchKernelGGL(k_compact, dim3(k.ntiles), dim3(kBlock), 0, st, k.masks, k.nw, k.st, idx, count, c->err_dev,
+                       stall);
     return launch_check("k_compact");
 }
 
@@ -2999,21 +2994,48 @@ DecOut make_dec_out(const rsk_decode_out *o, uint64_t *masks) {
     return d;
 }
 
+bool tcp_out_ok(const rsk_tcpinfo_out *t) {
+    return t->src && t->dst && t->sp && t->dp && t->seq && t->ack && t->flag && t->parse_status && t->cap_pay_off &&
+           t->cap_pay_len;
+}
+
+// the ten TcpInfo columns of ParseArgs / SyncArgs
+template <class A>
+void fill_tcp_out(A &a, const rsk_tcpinfo_out *t) {
+    a.src = t->src; a.dst = t->dst; a.sp = t->sp; a.dp = t->dp; a.seq = t->seq; a.ack = t->ack;
+    a.flag = t->flag; a.pst = t->parse_status; a.cpo = t->cap_pay_off; a.cpl = t->cap_pay_len;
+}
+
+// The arguments of an n-packet call from the ABI structs (rsk_encode_batch, rsk_encode_wire_batch);
+// false (RSK_EINVAL): a required array is null, or `id` is not 8-byte aligned.
+bool enc_args(uint32_t n, const rsk_encode_in *in, const rsk_encode_out *out, EncArgs &a) {
+    if (!in->payload_arena || !in->pay_off || !in->pay_len || !in->cmd || !in->conv || !in->conn_key ||
+        !out->frame_arena || !out->frame_off || !out->status)
+        return false;
+    if (in->id && (reinterpret_cast<uintptr_t>(in->id) & 7u)) return false;
+    a.payload = in->payload_arena; a.pay_off = in->pay_off; a.pay_len = in->pay_len; a.cmd = in->cmd;
+    a.conv = in->conv; a.conn_key = in->conn_key; a.id = in->id;
+    a.frame = out->frame_arena; a.frame_off = out->frame_off; a.status = out->status;
+    std::memcpy(&a.id_lo, in->id_uniform, 4);
+    std::memcpy(&a.id_hi, in->id_uniform + 4, 4);
+    a.n = n;
+    a.pad = (out->flags & RSK_ENC_ZERO_PAD128) ? 7u : (out->flags & RSK_ENC_ZERO_PAD16) ? 4u : 0u;
+    return true;
+}
+
+// Blocks of a per-set kernel (set_packet's mapping): every wave that owns at least one packet (the last
+// super-block may be partial: its wave wl owns packets iff wl * kSetGrp < the packets left).
+unsigned enc_grid(uint64_t n) {
+    const uint64_t per_sb = (uint64_t)kSetSbw * 64u, rest = n % per_sb;
+    const uint64_t waves = n / per_sb * kSetSbw + std::min<uint64_t>(kSetSbw, (rest + kSetGrp - 1) / kSetGrp);
+    return (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
+}
+
 }  // namespace
 
 // =============================================================================================
 // C ABI
 // =============================================================================================
-namespace {
-// Blocks of k_encode<.., GRP, SBW>: every wave that owns at least one packet (the last super-block
-// may be partial: its wave wl owns packets iff wl * GRP < the packets left).
-unsigned enc_grid(uint64_t n, uint32_t grp, uint32_t sbw) {
-    const uint64_t per_sb = (uint64_t)sbw * 64u, rest = n % per_sb;
-    const uint64_t waves = n / per_sb * sbw + std::min<uint64_t>(sbw, (rest + grp - 1) / grp);
-    return (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-}
-}  // namespace
-
 extern "C" {
 
 const char *rsk_last_error(void) { return g_last_error; }
@@ -3278,7 +3300,7 @@ static unsigned os_grid(int device) {
     unsigned g = cached[d].load(std::memory_order_relaxed);
     if (g) return g;
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_encode_os<3>, kBlock, 0) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_encode_os, kBlock, 0) != hipSuccess || per_cu < 1)
         per_cu = 1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
     (void)hipGetLastError();
@@ -3287,30 +3309,28 @@ static unsigned os_grid(int device) {
     return g;
 }
 
+// The statistic for the next call's choice, behind every call on a per-set path (a sample
+// every 256th call left a context that switched from short to long frames on the flat-only kernel
+// for up to 255 calls), unless the call is being captured (a graph replays the path it was captured
+// with).  One 64-thread launch behind the encode: the per-set kernel itself carries no pointer for
+// it (one more argument cost C4 12 % through SGPR spills, see enc_sample).
+static void sample_next(rsk_ctx *c, uint32_t n, const uint16_t *pay_len, hipStream_t st, const uint64_t *frame_off,
+                        uint32_t pad) {
+    if (c->enc_path == 0 && c->enc_stat_dev && n >= kTwoPassMinPackets && !rsk::capturing(st))
+        hipLaunchKernelGGL(k_enc_sample, dim3(1), dim3(64), 0, st, pay_len, n, c->enc_stat_dev, frame_off, pad);
+}
+
 int rsk_encode_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const rsk_encode_out *out,
                      void *stream) {
     if (!c || !in || !out) return RSK_EINVAL;
     if (n == 0) return RSK_OK;
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
-    if (!in->payload_arena || !in->pay_off || !in->pay_len || !in->cmd || !in->conv || !in->conn_key ||
-        !out->frame_arena || !out->frame_off || !out->status)
-        return RSK_EINVAL;
-    if (in->id && (reinterpret_cast<uintptr_t>(in->id) & 7u)) return RSK_EINVAL;
+    EncArgs a;
+    if (!enc_args(n, in, out, a)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    EncArgs a;
-    a.payload = in->payload_arena; a.pay_off = in->pay_off; a.pay_len = in->pay_len; a.cmd = in->cmd;
-    a.conv = in->conv; a.conn_key = in->conn_key; a.id = in->id;
-    a.frame = out->frame_arena; a.frame_off = out->frame_off; a.status = out->status;
-    std::memcpy(&a.id_lo, in->id_uniform, 4);
-    std::memcpy(&a.id_hi, in->id_uniform + 4, 4);
-    a.n = n;
-    a.pad = (out->flags & RSK_ENC_ZERO_PAD128) ? 7u : (out->flags & RSK_ENC_ZERO_PAD16) ? 4u : 0u;
-    const uint64_t waves = (n + 63ull) / 64ull;
-    const unsigned grid = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 gd(grid), bd(kBlock);
-    (void)gd;
+    const dim3 bd(kBlock);
     const int path = enc_path(c, n, in->pay_len, st, out->frame_off, a.pad);
     if (path < 0) return path;
     if (path == RSK_ENC_PATH_TWO_PASS) {
@@ -3323,10 +3343,10 @@ int rsk_encode_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const rsk_
                 m.bfirst = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(hp) + 32ull * n);
                 m.ctl = m.bfirst + os_bcap(n);
                 m.bcap = os_bcap(n);
-                m.epoch = ++c->os_epoch;
-                hipLaunchKernelGGL(k_encode_heads_os<0>, dim3(grid_for(n)), bd, 0, st, a, c->ks, static_cast<uint4 *>(hp),
+                m.epoch = c->os_epoch.fetch_add(1u, std::memory_order_relaxed) + 1u;
+                hipLaunchKernelGGL(k_encode_heads_os, dim3(grid_for(n)), bd, 0, st, a, c->ks, static_cast<uint4 *>(hp),
                                    c->enc_stat_dev, (uint64_t)n, m);
-                hipLaunchKernelGGL(k_encode_os<3>, dim3(os_grid(c->device)), bd, 0, st, a, static_cast<const uint4 *>(hp),
+                hipLaunchKernelGGL(k_encode_os, dim3(os_grid(c->device)), bd, 0, st, a, static_cast<const uint4 *>(hp),
                                    (uint64_t)n, m.bfirst, m.ctl, m.epoch);
                 c->enc_last_path.store(2, std::memory_order_relaxed);
                 c->enc_last_k.store(-1, std::memory_order_relaxed);
@@ -3338,16 +3358,16 @@ int rsk_encode_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const rsk_
             for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
                 EncArgs ac = a;
                 ac.n = (uint32_t)std::min<uint64_t>(n, c0 + chunk);
-                hipLaunchKernelGGL(k_encode_heads<0>, dim3(grid_for(ac.n - c0)), bd, 0, st, ac, c->ks,
+                hipLaunchKernelGGL(k_encode_heads, dim3(grid_for(ac.n - c0)), bd, 0, st, ac, c->ks,
                                    static_cast<uint4 *>(hp), c0 == 0 ? c->enc_stat_dev : nullptr, c0, (uint64_t)n);
                 for (uint64_t b0 = c0; b0 < ac.n; b0 += kCopyMaxPackets) {  // one launch up to 2^25 packets
                     const uint64_t m = ac.n - b0 < kCopyMaxPackets ? ac.n - b0 : kCopyMaxPackets;
                     const dim3 cg((unsigned)((m + 4ull * ck - 1ull) / (4ull * ck)));
                     const uint32_t *hr = static_cast<const uint32_t *>(hp);
                     const uint64_t nr = n;
-                    if (ck == 2) hipLaunchKernelGGL((k_encode_copy<3, 2>), cg, bd, 0, st, ac, hr, b0, nr);
-                    else if (ck == 4) hipLaunchKernelGGL((k_encode_copy<3, 4>), cg, bd, 0, st, ac, hr, b0, nr);
-                    else hipLaunchKernelGGL((k_encode_copy<3, 1>), cg, bd, 0, st, ac, hr, b0, nr);
+                    if (ck == 2) hipLaunchKernelGGL(k_encode_copy<2>, cg, bd, 0, st, ac, hr, b0, nr);
+                    else if (ck == 4) hipLaunchKernelGGL(k_encode_copy<4>, cg, bd, 0, st, ac, hr, b0, nr);
+                    else hipLaunchKernelGGL(k_encode_copy<1>, cg, bd, 0, st, ac, hr, b0, nr);
                 }
             }
             c->enc_last_path.store(2, std::memory_order_relaxed);
@@ -3359,23 +3379,16 @@ int rsk_encode_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const rsk_
     if (path == RSK_ENC_PATH_SHORT) {
         // batches of short frames: the per-set kernel with every set on the flat chunk list, compiled
         // without the per-packet copy (fewer VGPRs, more waves per SIMD; profiles/r04ac_short_path.json)
-        hipLaunchKernelGGL((k_encode<19, 4, 2, 8, 1024>), dim3(enc_grid(n, 8, 1024)), bd, 0, st, a, c->ks);
+        hipLaunchKernelGGL((k_encode<19, 4, 2>), dim3(enc_grid(n)), bd, 0, st, a, c->ks);
         c->enc_last_path.store(RSK_ENC_PATH_SHORT, std::memory_order_relaxed);
     } else {
         // the per-set kernel: per-wave hybrid (flat chunk list for short frames, with the tag behind the
         // first chunk loads; software-pipelined one-load DPP per-packet copy, 4 packets per batch, for
         // the rest), tag in the copy loop for long-frame sets, per-set store policy
-        hipLaunchKernelGGL((k_encode<11, 4, 4, 8, 1024>), dim3(enc_grid(n, 8, 1024)), bd, 0, st, a, c->ks);
+        hipLaunchKernelGGL((k_encode<11, 4, 4>), dim3(enc_grid(n)), bd, 0, st, a, c->ks);
         c->enc_last_path.store(RSK_ENC_PATH_PER_SET, std::memory_order_relaxed);
     }
-    // the statistic for the next call, on every call this path takes (a sample every 256th
-    // call left a context that switched from short to long frames on the flat-only kernel for up to 255
-    // calls), unless the call is being captured (a graph replays the path it was captured with).  One
-    // 64-thread launch behind the encode: the per-set kernel itself carries no pointer for it (one more
-    // argument cost C4 12 % through SGPR spills, gpurun_out/r04o).
-    if (c->enc_path == 0 && c->enc_stat_dev && n >= kTwoPassMinPackets && !rsk::capturing(st))
-        hipLaunchKernelGGL(k_enc_sample, dim3(1), dim3(64), 0, st, in->pay_len, n, c->enc_stat_dev, out->frame_off,
-                           a.pad);
+    sample_next(c, n, in->pay_len, st, out->frame_off, a.pad);
     return launch_check("k_encode");
 }
 
@@ -3398,8 +3411,10 @@ static int wire_path(rsk_ctx *c, uint32_t n, const uint16_t *pay_len, hipStream_
     return mean < kWireTwoPassFrom || (eth && mean >= kWireEthPerSetFrom) ? RSK_ENC_PATH_PER_SET
                                                                           : RSK_ENC_PATH_TWO_PASS;
 }
+// packets per copy wave: forced (rsk__set_copy_k; -1, the framing encode's output-stationary copy, has
+// no wire form and counts as 0 here), else by the sampled mean payload
 static int wire_k(rsk_ctx *c, bool eth) {
-    if (c->copy_k) return c->copy_k;
+    if (c->copy_k > 0) return c->copy_k;
     const uint32_t s = sampled_mean(c);
     const uint32_t mean = (s & kStatValid) ? s & kStatMean : 1400u;
     return eth || mean < kWireK2From ? 4 : 2;
@@ -3410,28 +3425,19 @@ int rsk_encode_wire_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const
     if (!c || !in || !wire || !out) return RSK_EINVAL;
     if (n == 0) return RSK_OK;
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
-    if (!in->payload_arena || !in->pay_off || !in->pay_len || !in->cmd || !in->conv || !in->conn_key ||
-        !out->frame_arena || !out->frame_off || !out->status || !wire->src || !wire->dst || !wire->sp ||
-        !wire->dp || !wire->seq || !wire->ack || !wire->flag || !wire->ip_id)
+    EncArgs a;
+    if (!enc_args(n, in, out, a)) return RSK_EINVAL;
+    if (!wire->src || !wire->dst || !wire->sp || !wire->dp || !wire->seq || !wire->ack || !wire->flag || !wire->ip_id)
         return RSK_EINVAL;
-    if (in->id && (reinterpret_cast<uintptr_t>(in->id) & 7u)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    EncArgs a;
-    a.payload = in->payload_arena; a.pay_off = in->pay_off; a.pay_len = in->pay_len; a.cmd = in->cmd;
-    a.conv = in->conv; a.conn_key = in->conn_key; a.id = in->id;
-    a.frame = out->frame_arena; a.frame_off = out->frame_off; a.status = out->status;
-    std::memcpy(&a.id_lo, in->id_uniform, 4);
-    std::memcpy(&a.id_hi, in->id_uniform + 4, 4);
-    a.n = n;
-    a.pad = (out->flags & RSK_ENC_ZERO_PAD128) ? 7u : (out->flags & RSK_ENC_ZERO_PAD16) ? 4u : 0u;
     WireArgs w;
     w.src = wire->src; w.dst = wire->dst; w.sp = wire->sp; w.dp = wire->dp; w.seq = wire->seq;
     w.ack = wire->ack; w.flag = wire->flag; w.ip_id = wire->ip_id;
     uint8_t eth[16] = {0};
     std::memcpy(eth, wire->eth, 14);
     std::memcpy(w.eth, eth, 16);
-    const unsigned grid = enc_grid(n, 8, 1024);
+    const unsigned grid = enc_grid(n);
     const hipStream_t st = (hipStream_t)stream;
     const bool eth14 = wire->with_eth != 0;
     // the encode path the context is held to (rsk_set_encode_path: two-pass, or else the per-set wire
@@ -3458,7 +3464,7 @@ int rsk_encode_wire_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const
                 if (eth14) hipLaunchKernelGGL(k_wire_heads<14>, dim3(grid_for(m)), bd, 0, st, ac, w, c->ks, rec, stat, c0, chunk);
                 else hipLaunchKernelGGL(k_wire_heads<0>, dim3(grid_for(m)), bd, 0, st, ac, w, c->ks, rec, stat, c0, chunk);
                 const dim3 cg((unsigned)((m + 4ull * ck - 1ull) / (4ull * ck)));  // m <= kWireChunk: one launch
-#define RSK_WCOPY(E, K) hipLaunchKernelGGL((k_wire_copy<E, 3, K>), cg, bd, 0, st, ac, rec, c0, c0, chunk)
+#define RSK_WCOPY(E, K) hipLaunchKernelGGL((k_wire_copy<E, K>), cg, bd, 0, st, ac, rec, c0, c0, chunk)
                 if (eth14) {
                     if (ck == 2) RSK_WCOPY(14, 2); else if (ck == 4) RSK_WCOPY(14, 4); else RSK_WCOPY(14, 1);
                 } else {
@@ -3481,10 +3487,7 @@ int rsk_encode_wire_batch(rsk_ctx *c, uint32_t n, const rsk_encode_in *in, const
 #undef RSK_WIRE
 #undef RSK_WIRE4
     c->enc_last_path.store(RSK_ENC_PATH_PER_SET, std::memory_order_relaxed);
-    // the statistic for the next call's choice (as rsk_encode_batch)
-    if (c->enc_path == 0 && c->enc_stat_dev && n >= kTwoPassMinPackets && !rsk::capturing(st))
-        hipLaunchKernelGGL(k_enc_sample, dim3(1), dim3(64), 0, st, in->pay_len, n, c->enc_stat_dev,
-                           (const uint64_t *)nullptr, 0u);
+    sample_next(c, n, in->pay_len, st, nullptr, 0u);  // as rsk_encode_batch
     return launch_check("k_encode_wire");
 }
 
@@ -3497,18 +3500,11 @@ int rsk_decode_batch(rsk_ctx *c, uint32_t n, const uint8_t *frame_arena, const u
     if (!frame_arena || !frame_off || !frame_len || !dec_out_ok(out)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = out->valid_idx || out->n_valid;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
-    DecArgs a{frame_arena, frame_off, frame_len, is_tcp_close, n};
-    DecOut d = make_dec_out(out, ck.masks);
-    hipLaunchKernelGGL(k_decode, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, d, c->ks);
-    int r = launch_check("k_decode");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, out->valid_idx, out->n_valid, (hipStream_t)stream);
+    const DecArgs a{frame_arena, frame_off, frame_len, is_tcp_close, n};
+    const hipStream_t st = (hipStream_t)stream;
+    return launch_compacted(c, n, out->valid_idx, out->n_valid, st, "k_decode", [&](uint64_t *masks) {
+        hipLaunchKernelGGL(k_decode, dim3(grid_for(n)), dim3(kBlock), 0, st, a, make_dec_out(out, masks), c->ks);
+    });
 }
 
 int rsk_encode_headers_batch(rsk_ctx *c, uint32_t n, const rsk_encode_hdr_in *in, uint8_t *hdr, int32_t *status,
@@ -3540,30 +3536,11 @@ int rsk_decode_headers_batch(rsk_ctx *c, uint32_t n, const uint8_t *hdr, const u
     if (reinterpret_cast<uintptr_t>(hdr) & 15u) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = out->valid_idx || out->n_valid;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
-    DecArgs a{hdr, nullptr, frame_len, is_tcp_close, n};
-    DecOut d = make_dec_out(out, ck.masks);
-    hipLaunchKernelGGL(k_decode_hdr, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, d, c->ks);
-    int r = launch_check("k_decode_hdr");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, out->valid_idx, out->n_valid, (hipStream_t)stream);
-}
-
-// Host: the 32-B decode slot of one received frame (EncHead::DecodeBuf reads frame[8] = len; the
-// hashed byte is frame[8 + len] when that lies inside the frame, RConn.cpp:64-75).
-void rsk_stage_decode_header(const uint8_t *frame, int nread, uint8_t *slot) {
-    const int k = nread < 0 ? 0 : (nread < 32 ? nread : 32);
-    std::memcpy(slot, frame, (size_t)k);
-    if (k < 32) std::memset(slot + k, 0, (size_t)(32 - k));
-    if (nread > 8) {
-        const int at = 8 + frame[8];
-        if (at < nread) slot[31] = frame[at];
-    }
+    const DecArgs a{hdr, nullptr, frame_len, is_tcp_close, n};
+    const hipStream_t st = (hipStream_t)stream;
+    return launch_compacted(c, n, out->valid_idx, out->n_valid, st, "k_decode_hdr", [&](uint64_t *masks) {
+        hipLaunchKernelGGL(k_decode_hdr, dim3(grid_for(n)), dim3(kBlock), 0, st, a, make_dec_out(out, masks), c->ks);
+    });
 }
 
 namespace {
@@ -3575,37 +3552,26 @@ int parse_decode(rsk_ctx *c, uint32_t n, const uint8_t *cap_arena, const uint64_
     if (n == 0) return empty_batch(c, dec->n_valid, stream);
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
     if (!cap_arena || (!slot && !cap_off) || !wire_len || !cap_len || !dec_out_ok(dec)) return RSK_EINVAL;
-    if (!tcp->src || !tcp->dst || !tcp->sp || !tcp->dp || !tcp->seq || !tcp->ack || !tcp->flag ||
-        !tcp->parse_status || !tcp->cap_pay_off || !tcp->cap_pay_len)
-        return RSK_EINVAL;
+    if (!tcp_out_ok(tcp)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = dec->valid_idx || dec->n_valid;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
     ParseArgs a;
     a.cap = cap_arena; a.cap_off = cap_off; a.wire_len = wire_len; a.cap_len = cap_len;
-    a.src = tcp->src; a.dst = tcp->dst; a.sp = tcp->sp; a.dp = tcp->dp; a.seq = tcp->seq; a.ack = tcp->ack;
-    a.flag = tcp->flag; a.pst = tcp->parse_status; a.cpo = tcp->cap_pay_off; a.cpl = tcp->cap_pay_len;
-    a.datalink = datalink; a.flags = flags; a.n = n;
-    DecOut d = make_dec_out(dec, ck.masks);
-    a.slot = slot;
+    fill_tcp_out(a, tcp);
+    a.datalink = datalink; a.flags = flags; a.n = n; a.slot = slot;
     const bool sl = slot != 0;
     const hipStream_t st = (hipStream_t)stream;
-    const dim3 gd(grid_for(n)), bd(kBlock);
-    if (datalink == RSK_DLT_EN10MB) {
-        if (sl) hipLaunchKernelGGL((k_parse_decode<14, true>), gd, bd, 0, st, a, d, c->ks);
-        else hipLaunchKernelGGL((k_parse_decode<14, false>), gd, bd, 0, st, a, d, c->ks);
-    } else {
-        if (sl) hipLaunchKernelGGL((k_parse_decode<4, true>), gd, bd, 0, st, a, d, c->ks);
-        else hipLaunchKernelGGL((k_parse_decode<4, false>), gd, bd, 0, st, a, d, c->ks);
-    }
-    int r = launch_check("k_parse_decode");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, dec->valid_idx, dec->n_valid, (hipStream_t)stream);
+    return launch_compacted(c, n, dec->valid_idx, dec->n_valid, st, "k_parse_decode", [&](uint64_t *masks) {
+        const DecOut d = make_dec_out(dec, masks);
+        const dim3 gd(grid_for(n)), bd(kBlock);
+        if (datalink == RSK_DLT_EN10MB) {
+            if (sl) hipLaunchKernelGGL((k_parse_decode<14, true>), gd, bd, 0, st, a, d, c->ks);
+            else hipLaunchKernelGGL((k_parse_decode<14, false>), gd, bd, 0, st, a, d, c->ks);
+        } else {
+            if (sl) hipLaunchKernelGGL((k_parse_decode<4, true>), gd, bd, 0, st, a, d, c->ks);
+            else hipLaunchKernelGGL((k_parse_decode<4, false>), gd, bd, 0, st, a, d, c->ks);
+        }
+    });
 }
 }  // namespace
 
@@ -3629,27 +3595,18 @@ int rsk_syncinput_decode_batch(rsk_ctx *c, uint32_t n, const uint8_t *rec_arena,
     if (n == 0) return empty_batch(c, dec->n_valid, stream);
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
     if (!rec_arena || !rec_off || !nread || !dec_out_ok(dec)) return RSK_EINVAL;
-    if (!tcp->src || !tcp->dst || !tcp->sp || !tcp->dp || !tcp->seq || !tcp->ack || !tcp->flag ||
-        !tcp->parse_status || !tcp->cap_pay_off || !tcp->cap_pay_len)
-        return RSK_EINVAL;
+    if (!tcp_out_ok(tcp)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = dec->valid_idx || dec->n_valid;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
     SyncArgs a;
     a.rec = rec_arena; a.rec_off = rec_off; a.nread = nread;
-    a.src = tcp->src; a.dst = tcp->dst; a.sp = tcp->sp; a.dp = tcp->dp; a.seq = tcp->seq; a.ack = tcp->ack;
-    a.flag = tcp->flag; a.pst = tcp->parse_status; a.cpo = tcp->cap_pay_off; a.cpl = tcp->cap_pay_len;
+    fill_tcp_out(a, tcp);
     a.n = n;
-    const DecOut d = make_dec_out(dec, ck.masks);
-    hipLaunchKernelGGL(k_syncinput_decode, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, d, c->ks);
-    int r = launch_check("k_syncinput_decode");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, dec->valid_idx, dec->n_valid, (hipStream_t)stream);
+    const hipStream_t st = (hipStream_t)stream;
+    return launch_compacted(c, n, dec->valid_idx, dec->n_valid, st, "k_syncinput_decode", [&](uint64_t *masks) {
+        hipLaunchKernelGGL(k_syncinput_decode, dim3(grid_for(n)), dim3(kBlock), 0, st, a, make_dec_out(dec, masks),
+                           c->ks);
+    });
 }
 
 int rsk_filter_parse_decode_batch(rsk_ctx *c, uint32_t n, const uint8_t *cap_arena, const uint64_t *cap_off,
@@ -3662,31 +3619,20 @@ int rsk_filter_parse_decode_batch(rsk_ctx *c, uint32_t n, const uint8_t *cap_are
     if (n == 0) return empty_batch(c, dec->n_valid, stream);
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
     if (!cap_arena || !cap_off || !wire_len || !cap_len || !match || !dec_out_ok(dec)) return RSK_EINVAL;
-    if (!tcp->src || !tcp->dst || !tcp->sp || !tcp->dp || !tcp->seq || !tcp->ack || !tcp->flag ||
-        !tcp->parse_status || !tcp->cap_pay_off || !tcp->cap_pay_len)
-        return RSK_EINVAL;
+    if (!tcp_out_ok(tcp)) return RSK_EINVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = dec->valid_idx || dec->n_valid;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
     ParseArgs a;
     a.cap = cap_arena; a.cap_off = cap_off; a.wire_len = wire_len; a.cap_len = cap_len;
-    a.src = tcp->src; a.dst = tcp->dst; a.sp = tcp->sp; a.dp = tcp->dp; a.seq = tcp->seq; a.ack = tcp->ack;
-    a.flag = tcp->flag; a.pst = tcp->parse_status; a.cpo = tcp->cap_pay_off; a.cpl = tcp->cap_pay_len;
+    fill_tcp_out(a, tcp);
     a.datalink = datalink; a.flags = flags; a.n = n; a.slot = 0;
-    DecOut d = make_dec_out(dec, ck.masks);
     const hipStream_t st = (hipStream_t)stream;
-    if (datalink == RSK_DLT_EN10MB)
-        hipLaunchKernelGGL(k_filter_parse_decode<14>, dim3(grid_for(n)), dim3(kBlock), 0, st, a, d, c->ks, match, *f);
-    else
-        hipLaunchKernelGGL(k_filter_parse_decode<4>, dim3(grid_for(n)), dim3(kBlock), 0, st, a, d, c->ks, match, *f);
-    int r = launch_check("k_filter_parse_decode");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, dec->valid_idx, dec->n_valid, (hipStream_t)stream);
+    return launch_compacted(c, n, dec->valid_idx, dec->n_valid, st, "k_filter_parse_decode", [&](uint64_t *masks) {
+        const DecOut d = make_dec_out(dec, masks);
+        const dim3 gd(grid_for(n)), bd(kBlock);
+        if (datalink == RSK_DLT_EN10MB) hipLaunchKernelGGL(k_filter_parse_decode<14>, gd, bd, 0, st, a, d, c->ks, match, *f);
+        else hipLaunchKernelGGL(k_filter_parse_decode<4>, gd, bd, 0, st, a, d, c->ks, match, *f);
+    });
 }
 
 int rsk_capture_filter_batch(rsk_ctx *c, uint32_t n, const uint8_t *cap_arena, const uint64_t *cap_off,
@@ -3699,58 +3645,17 @@ int rsk_capture_filter_batch(rsk_ctx *c, uint32_t n, const uint8_t *cap_arena, c
     if (n > RSK_MAX_BATCH) return RSK_EINVAL;  // grids of one lane per packet
     DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    const bool compact = match_idx || n_match;
-    Compact ck;
-    if (compact) {
-        int r = ensure_compact(c, n, (hipStream_t)stream, ck);
-        if (r) return r;
-    }
     FiltArgs a;
     a.cap = cap_arena; a.cap_off = cap_off; a.cap_len = cap_len; a.match = match; a.n = n;
-    DecOut d;
-    std::memset(&d, 0, sizeof d);
-    d.masks = ck.masks;
-    if (datalink == RSK_DLT_EN10MB)
-        hipLaunchKernelGGL(k_capture_filter<14>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, d, *f);
-    else
-        hipLaunchKernelGGL(k_capture_filter<4>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a, d, *f);
-    int r = launch_check("k_capture_filter");
-    if (r || !compact) return r;
-    return run_compaction(c, ck, match_idx, n_match, (hipStream_t)stream);
-}
-
-// BuildFilterStr (cap/cap_util.cpp:67-144) with proto "tcp" (cap/RCap.cpp:64)
-int rsk_filter_str(const rsk_capture_filter *f, char *buf, size_t buf_len) {
-    if (!f || !buf) return -1;
-    auto ip = [](uint32_t v) {
-        return std::to_string(v & 255u) + "." + std::to_string((v >> 8) & 255u) + "." +
-               std::to_string((v >> 16) & 255u) + "." + std::to_string(v >> 24);
-    };
-    auto ports = [](const rsk_port_list &pl, const char *dir) -> std::string {
-        if (pl.n_single == 0 && pl.n_range == 0) return "";
-        std::string s = "(";
-        for (uint32_t q = 0; q < pl.n_single && q < RSK_FILTER_MAX_PORTS; ++q)
-            s += std::string(" or ") + dir + " port " + std::to_string(pl.single[q]);
-        for (uint32_t q = 0; q < pl.n_range && q < RSK_FILTER_MAX_PORTS; ++q)
-            s += std::string(" or ") + dir + " portrange " + std::to_string(pl.range[q][0]) + "-" +
-                 std::to_string(pl.range[q][1]);
-        s += " )";
-        s.replace(s.find("or"), 2, "");  // the reference removes the first "or"
-        return " and " + s;
-    };
-    std::string out = "tcp";
-    if (f->has_src_ip) out += " and  (ip src " + ip(f->src_ip) + ")";
-    if (f->has_dst_ip) out += " and  (ip dst " + ip(f->dst_ip) + ")";
-    out += ports(f->src_ports, "src");
-    out += ports(f->dst_ports, "dst");
-    if (f->is_server) {
-        std::string s = out;
-        for (size_t pos = s.find("dst"); pos != std::string::npos; pos = s.find("dst")) s.replace(pos, 3, "src");
-        out = "((tcp[tcpflags] & tcp-syn != 0) and " + s + ") or (" + out + "and (tcp[tcpflags] & (tcp-syn) == 0))";
-    }
-    if (out.size() + 1 > buf_len) return -1;
-    std::memcpy(buf, out.c_str(), out.size() + 1);
-    return (int)out.size();
+    const hipStream_t st = (hipStream_t)stream;
+    return launch_compacted(c, n, match_idx, n_match, st, "k_capture_filter", [&](uint64_t *masks) {
+        DecOut d;
+        std::memset(&d, 0, sizeof d);
+        d.masks = masks;
+        const dim3 gd(grid_for(n)), bd(kBlock);
+        if (datalink == RSK_DLT_EN10MB) hipLaunchKernelGGL(k_capture_filter<14>, gd, bd, 0, st, a, d, *f);
+        else hipLaunchKernelGGL(k_capture_filter<4>, gd, bd, 0, st, a, d, *f);
+    });
 }
 
 int rsk_tcpinfo_encode_batch(rsk_ctx *c, uint32_t n, const uint32_t *src, const uint32_t *dst,
@@ -3775,13 +3680,6 @@ int rsk_fill_splitmix(void *dst, uint64_t nbytes, uint64_t seed, void *stream) {
     hipLaunchKernelGGL(k_fill_splitmix, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<uint8_t *>(dst), nbytes, seed);
     return launch_check("k_fill_splitmix");
-}
-
-uint64_t rsk_key_for_tcp(uint16_t sp, uint16_t dp) {
-    return 0x10000000ull | ((uint64_t)dp << 16) | (uint64_t)sp;  // KeyGenerator.cpp:16-25
-}
-uint64_t rsk_key_for_udp(uint16_t sp, uint16_t dp) {
-    return 0x20000000ull | ((uint64_t)dp << 16) | (uint64_t)sp;  // KeyGenerator.cpp:27-36
 }
 
 }  // extern "C"

@@ -161,7 +161,8 @@ def test_wire_two_pass_chunks_equal_per_set(codec, gpu, eth):
     ethb = bytes(range(14)) if eth else None
     outs = {}
     try:
-        for path, k in [(1, 0), (2, 1), (2, 2), (2, 4)]:
+        # (2, -1): the framing encode's output-stationary copy has no wire form; the wire build picks its own k
+        for path, k in [(1, 0), (2, 1), (2, 2), (2, 4), (2, -1)]:
             codec.set_encode_path(path)
             codec.set_copy_k(k)
             wire = torch.zeros(n * pitch, dtype=torch.uint8, device=gpu)
@@ -169,6 +170,8 @@ def test_wire_two_pass_chunks_equal_per_set(codec, gpu, eth):
             codec.output_wire_batch(w.payload, w.pay_off, w.pay_len, w.cmd, w.conv, w.conn_key, *fields, wire, woff, st,
                                     eth=ethb, id_uniform=workload.ID_UNIFORM, pad128=True)
             assert codec.last_encode_path == path
+            if k == -1:
+                assert codec.last_copy_k in (1, 2, 4)
             torch.cuda.synchronize()
             outs[(path, k)] = (wire, st)
             if path == 2:

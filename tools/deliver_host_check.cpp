@@ -13,9 +13,6 @@
 
 #include "rsk_codec.h"
 
-// rsk_host.cpp references this single-frame helper of the library (rsk_kernels.hip); unused here
-extern "C" void rsk_stage_decode_header(const uint8_t *, int, uint8_t *) {}
-
 static uint64_t rng_state = 0x5EED;
 static uint32_t rnd() {
     rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
