@@ -36,6 +36,13 @@
  *                            (server/SubGroup.cpp:31-50), ClientGroup::OnRecv by conv (client/ClientGroup.cpp:66-80)
  *   rsk_deliver_batch     <- the per-packet payload copy of the consumers: SConn::OnRecv
  *                            (server/SConn.cpp:77-89), ClientGroup::send2Origin (client/ClientGroup.cpp:82-96)
+ *   rsk_conn_resolve_batch <- INetGroup::Input's lookup of a packet's INetConn by connKey, ConnOfIntKey
+ *                            (conn/INetGroup.cpp:57-83), below ServerGroup's per-IdBuf SNetGroup
+ *                            (server/ServerGroup.cpp:44-60)
+ *   rsk_conn_expand_batch <- INetConn::Output (conn/INetConn.cpp:30-39) handing FakeTcp's TcpInfo mInfo
+ *                            (conn/FakeTcp.cpp:14-50) to RawTcp::Output as the packet's addresses, ports,
+ *                            ack and flag
+ *   rsk_conn_table        <- INetGroup's mConnMap and the TcpInfo mInfo of each FakeTcp in it
  */
 #ifndef RSK_CODEC_H
 #define RSK_CODEC_H
@@ -598,6 +605,116 @@ int rsk_verify_wire_batch(rsk_ctx *ctx, uint32_t n, const rsk_verify_in *in, int
 /* Host twin (host pointers throughout; the same rule and outputs; nthreads as rsk_deliver_host; no
  * upper limit on n). */
 int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, const rsk_verify_out *out, int nthreads);
+
+/* ---- fake-TCP connection table: a packet's connection, a connection's TcpInfo -------------------- */
+/* The level the reference keeps between the codec and the leaves: INetGroup's map from connKey to
+ * INetConn (mConnMap, conn/INetGroup.cpp:57-83; one INetGroup per IdBuf on a server,
+ * server/ServerGroup.cpp:44-60) and the TcpInfo mInfo of every FakeTcp in it (conn/FakeTcp.cpp:14-50,
+ * conn/INetConn.cpp:30-39).  Here it is a table of `capacity` rows in caller-owned device columns plus
+ * one opaque index, so a batch carries connection indices only:
+ *   receive  parse_decode -> verify -> rsk_conn_resolve_batch -> conn[i], the conn / delivered columns of
+ *            rsk_tcp_recv_ack_batch(conn, hit, tcp->seq, capacity, tab.ack)
+ *   send     rsk_conn_expand_batch(conn) -> src, dst, sp, dp, ack, flag (rsk_wire_in) and conn_key, id
+ *            (rsk_encode_in); seq and ip_id from rsk_tcp_send_seq_batch(conn, status, capacity, tab.seq, ...)
+ * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
+ * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
+ * incremental insert or erase); an index that was not rebuilt after such a change gives lookups of
+ * the changed keys an unspecified row or RSK_CONN_NONE, never an access outside the table.  The other
+ * columns need no rebuild.  The arrays are the caller's and do not move, so a call captured into a
+ * hipGraph sees later row edits and rebuilds.
+ * The key of a row is its conn_key, or with RSK_CONN_BY_ID the pair (id, conn_key).  When two LIVE rows
+ * hold one key the lowest row is the key's connection, whatever order the device ran them in. */
+#define RSK_CONN_NONE     0xFFFFFFFFu
+#define RSK_CONN_MAX_ROWS 0x100000u /* 2^20 */
+#define RSK_CONN_BY_ID    0x1u   /* key = (IdBuf, connKey): a server, whose SNetGroup is per IdBuf
+                                    (server/ServerGroup.cpp:44-60); without it connKey alone: a client */
+#define RSK_CONN_LIVE     0x1u   /* state bit: the row holds a connection (it is in mConnMap)        */
+#define RSK_CONN_ALIVE    0x2u   /* state bit: INetConn::Alive()                                     */
+
+typedef struct rsk_conn_table {  /* device pointers, caller-owned, `capacity` rows */
+    uint32_t capacity, flags;    /* capacity in [1, RSK_CONN_MAX_ROWS]; flags: RSK_CONN_BY_ID or 0   */
+    const uint8_t  *state;       /* [C] RSK_CONN_LIVE | RSK_CONN_ALIVE bits */
+    const uint64_t *conn_key;    /* [C] INetConn::mIntKey */
+    const uint8_t  *id;          /* [C*8], 8-B aligned; BY_ID only, else may be NULL */
+    const uint32_t *src, *dst;   /* [C] TcpInfo as stored */
+    const uint16_t *sp, *dp;     /* [C] */
+    uint32_t *seq, *ack;         /* [C] the conn_seq / conn_ack of rsk_tcp_send_seq_batch /
+                                    rsk_tcp_recv_ack_batch with n_conn = capacity */
+    const uint8_t  *flag;        /* [C] TcpInfo::flag used when sending */
+    uint32_t *index;             /* opaque, rsk_conn_index_bytes(capacity, flags) bytes, 16-B aligned */
+} rsk_conn_table;
+
+/* Bytes of the index of a table (8 per row rounded up to a power of two, at least 16: an
+ * open-addressing table over the LIVE rows that always keeps half of its entries free, so a lookup of
+ * an absent key ends even when every row is LIVE); 0 for a capacity outside [1, RSK_CONN_MAX_ROWS] or
+ * unknown flags. */
+uint64_t rsk_conn_index_bytes(uint32_t capacity, uint32_t flags);
+/* Rebuilds tab->index from state, conn_key (and id): two launches of one kernel on `stream`, the first
+ * clearing the index, the second inserting the LIVE rows; *n_dup (device, may be NULL; written, not
+ * accumulated) = the LIVE rows that lost their key to a lower row.  No scratch.  RSK_EINVAL: a NULL
+ * ctx, tab, state, conn_key or index, id missing with BY_ID, unknown flags, a capacity outside
+ * [1, RSK_CONN_MAX_ROWS], an index that is not 16-B aligned, an id column that is not 8-B aligned. */
+int rsk_conn_index_build(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t *n_dup, void *stream);
+
+/* Receive: INetGroup::Input's lookup, once per batch.  Packet i is looked up iff status[i] ==
+ * RSK_RECV_VALID and cmd[i] == RSK_CMD_DATA (control packets never reach INetGroup::Input,
+ * conn/IAppGroup.cpp:80-95): conn[i] = the LIVE row with its key (whether or not RSK_CONN_ALIVE is set:
+ * Input does not ask Alive()), or RSK_CONN_NONE.  A packet that is not looked up gets conn NONE, hit 0,
+ * miss DROP, and its key fields are not read.
+ * `miss` is a status column of the looked-up packets whose key is unknown -- the ones the reference
+ * answers with ERR_NO_CONN and a SendNetConnRst (conn/IAppGroup.cpp:80-87) on a client, with
+ * CreateNetConn (server/SNetGroup.cpp:20-46) on a server: rsk_demux_batch(status = miss, ...,
+ * RSK_DEMUX_ID | RSK_DEMUX_CONN_KEY) -- RSK_DEMUX_CONN_KEY alone on a client -- lists the distinct
+ * missing keys in first-arrival order in seg_first, i.e. one reset per key, or the conns in the order
+ * CreateNetConn would make them.
+ * No scratch: one memset node (n_miss, when given) and one kernel, a linear chain that a hipGraph
+ * captures without a reserve.  n == 0 zeroes a given n_miss.  RSK_EINVAL: a NULL ctx, tab, in or out;
+ * a NULL status, conn_key or conn with n > 0; a NULL tab->conn_key or tab->index; id missing (in the
+ * table or in `in`) with BY_ID, or one that is not 8-B aligned; unknown flags; a capacity outside
+ * [1, RSK_CONN_MAX_ROWS]; n > RSK_MAX_BATCH. */
+typedef struct rsk_conn_resolve_in {
+    const int8_t   *status;    /* [n] dec->status */
+    const uint8_t  *cmd;       /* [n] dec->cmd, or NULL = all DATA */
+    const uint8_t  *id;        /* [n*8] dec->id (8-B aligned); required with BY_ID */
+    const uint64_t *conn_key;  /* [n] dec->conn_key */
+} rsk_conn_resolve_in;
+typedef struct rsk_conn_resolve_out {
+    uint32_t *conn;    /* [n] row, or RSK_CONN_NONE */
+    uint8_t  *hit;     /* [n] optional: 1 iff conn[i] != NONE (the `delivered` of rsk_tcp_recv_ack_batch) */
+    int8_t   *miss;    /* [n] optional: RSK_RECV_VALID iff looked up and not found, else RSK_RECV_DROP */
+    uint32_t *n_miss;  /* [1] optional, written not accumulated */
+} rsk_conn_resolve_out;
+int rsk_conn_resolve_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, const rsk_conn_resolve_in *in,
+                           const rsk_conn_resolve_out *out, void *stream);
+
+/* Send: what INetConn::Output and RawTcp::Output take from the connection the sender picked.  ok[i] = 1
+ * iff conn[i] < capacity and the row is LIVE and ALIVE; then every given column receives the row's
+ * value (ack as it is when the kernel runs: stream-ordered behind an earlier rsk_tcp_recv_ack_batch).
+ * Otherwise ok[i] = 0 and every given column receives zero: the caller picked a dead conn, which the
+ * reference's doSend drops before picking again (conn/INetGroup.cpp:111-135; the pick itself stays on
+ * the host, rand() is not reproducible on the device).  *n_bad = the packets with ok == 0 (written, not
+ * accumulated).  No scratch, one memset node and one kernel, as the resolve.
+ * RSK_EINVAL: a NULL ctx, tab, out or tab->state; a NULL conn or ok with n > 0; an output column whose
+ * table column is NULL; an id column (the table's or out->id) that is not 8-B aligned when out->id is
+ * given; unknown flags; a capacity outside [1, RSK_CONN_MAX_ROWS]; n > RSK_MAX_BATCH. */
+typedef struct rsk_conn_expand_out {   /* every array optional except ok */
+    uint32_t *src, *dst; uint16_t *sp, *dp; uint32_t *ack; uint8_t *flag;
+    uint64_t *conn_key; uint8_t *id /*[n*8], 8-B aligned*/;
+    uint8_t *ok;       /* [n] 1 iff conn[i] < capacity and the row is LIVE|ALIVE */
+    uint32_t *n_bad;   /* [1] optional: packets with ok == 0 */
+} rsk_conn_expand_out;
+int rsk_conn_expand_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, const uint32_t *conn,
+                          const rsk_conn_expand_out *out, void *stream);
+
+/* Host twins (host pointers throughout, the table's included; the same rules and outputs; nthreads as
+ * rsk_deliver_host; the build takes it for symmetry and runs on the caller's thread).  The index has
+ * one layout on both sides: one built here and copied to the device is valid there, and the reverse.
+ * The host twins read the IdBuf columns bytewise and accept any alignment of them. */
+int rsk_conn_index_build_host(const rsk_conn_table *tab, uint32_t *n_dup, int nthreads);
+int rsk_conn_resolve_host(const rsk_conn_table *tab, uint32_t n, const rsk_conn_resolve_in *in,
+                          const rsk_conn_resolve_out *out, int nthreads);
+int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *conn,
+                         const rsk_conn_expand_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

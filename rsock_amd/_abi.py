@@ -43,6 +43,10 @@ DEMUX_ID, DEMUX_CONN_KEY, DEMUX_CONV, DEMUX_DST, DEMUX_CMD_BARRIER = 0x01, 0x02,
 DEMUX_GROUP_BARRIER = 0x20
 CSUM_IP_CHECKED, CSUM_IP_OK, CSUM_TCP_CHECKED, CSUM_TCP_OK, CSUM_TCP_TRUNC = 0x01, 0x02, 0x04, 0x08, 0x10
 VERIFY_MAX_BATCH = 0x1FFFFFE0
+CONN_NONE = 0xFFFFFFFF
+CONN_MAX_ROWS = 1 << 20
+CONN_BY_ID = 0x1
+CONN_LIVE, CONN_ALIVE = 0x1, 0x2
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -138,6 +142,25 @@ class VerifyOut(ctypes.Structure):
     _fields_ = [("csum", _vp), ("status_out", _vp), ("n_bad", _vp)]
 
 
+class ConnTable(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("state", _vp), ("conn_key", _vp),
+                ("id", _vp), ("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("seq", _vp), ("ack", _vp),
+                ("flag", _vp), ("index", _vp)]
+
+
+class ConnResolveIn(ctypes.Structure):
+    _fields_ = [("status", _vp), ("cmd", _vp), ("id", _vp), ("conn_key", _vp)]
+
+
+class ConnResolveOut(ctypes.Structure):
+    _fields_ = [("conn", _vp), ("hit", _vp), ("miss", _vp), ("n_miss", _vp)]
+
+
+class ConnExpandOut(ctypes.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("ack", _vp), ("flag", _vp), ("conn_key", _vp),
+                ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -206,6 +229,19 @@ SIGNATURES = [
      [_vp, ctypes.c_uint32, ctypes.POINTER(VerifyIn), ctypes.c_int, ctypes.POINTER(VerifyOut), _vp]),
     ("rsk_verify_wire_host", ctypes.c_int,
      [ctypes.c_uint32, ctypes.POINTER(VerifyIn), ctypes.c_int, ctypes.POINTER(VerifyOut), ctypes.c_int]),
+    ("rsk_conn_index_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_conn_index_build", ctypes.c_int, [_vp, ctypes.POINTER(ConnTable), _vp, _vp]),
+    ("rsk_conn_resolve_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ConnResolveIn), ctypes.POINTER(ConnResolveOut),
+      _vp]),
+    ("rsk_conn_expand_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.c_uint32, _vp, ctypes.POINTER(ConnExpandOut), _vp]),
+    ("rsk_conn_index_build_host", ctypes.c_int, [ctypes.POINTER(ConnTable), _vp, ctypes.c_int]),
+    ("rsk_conn_resolve_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ConnResolveIn), ctypes.POINTER(ConnResolveOut),
+      ctypes.c_int]),
+    ("rsk_conn_expand_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.c_uint32, _vp, ctypes.POINTER(ConnExpandOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

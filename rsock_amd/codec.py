@@ -286,6 +286,118 @@ def verify_wire_host(cap: np.ndarray, cap_off: np.ndarray, cap_len: np.ndarray, 
     return csum[:n], None if sout is None else sout[:n], int(nb[0])
 
 
+_CONN_COLUMNS = (("state", torch.uint8, 1), ("conn_key", torch.int64, 1), ("id", torch.uint8, 8),
+                 ("src", torch.int32, 1), ("dst", torch.int32, 1), ("sp", torch.int16, 1), ("dp", torch.int16, 1),
+                 ("seq", torch.int32, 1), ("ack", torch.int32, 1), ("flag", torch.uint8, 1))
+
+
+@dataclass
+class ConnTable:
+    """The fake-TCP connection table (rsk_conn_table): `capacity` rows in columns of torch tensors (signed
+    storage of the unsigned C types, as the other buffers here) plus the opaque index.  On a device the
+    batch calls of Codec take it; on "cpu" the host twins below do.  Rows are edited with ordinary tensor
+    writes; after any change to state, conn_key or id call rebuild()."""
+
+    capacity: int
+    by_id: bool
+    state: torch.Tensor     # uint8: CONN_LIVE | CONN_ALIVE
+    conn_key: torch.Tensor  # int64 storage of u64
+    id: torch.Tensor | None  # capacity * 8 bytes; by_id only
+    src: torch.Tensor
+    dst: torch.Tensor
+    sp: torch.Tensor
+    dp: torch.Tensor
+    seq: torch.Tensor       # the conn_seq of tcp_send_seq_batch
+    ack: torch.Tensor       # the conn_ack of tcp_recv_ack_batch
+    flag: torch.Tensor
+    index: torch.Tensor     # opaque, rsk_conn_index_bytes bytes
+
+    @classmethod
+    def alloc(cls, capacity: int, device, by_id: bool = False) -> "ConnTable":
+        nbytes = lib().rsk_conn_index_bytes(capacity, _abi.CONN_BY_ID if by_id else 0)
+        if nbytes == 0:
+            raise RskError(f"rsk_conn_index_bytes: bad capacity {capacity}")
+        cols = {name: torch.zeros(capacity * k, dtype=dt, device=device) for name, dt, k in _CONN_COLUMNS}
+        if not by_id:
+            cols["id"] = None
+        return cls(capacity=int(capacity), by_id=bool(by_id), index=torch.empty(nbytes // 4, dtype=torch.int32,
+                                                                               device=device), **cols)
+
+    @property
+    def flags(self) -> int:
+        return _abi.CONN_BY_ID if self.by_id else 0
+
+    def abi(self) -> _abi.ConnTable:
+        return _abi.ConnTable(self.capacity, self.flags, *[_ptr(getattr(self, name)) for name, _, _ in _CONN_COLUMNS],
+                              _ptr(self.index))
+
+    def load(self, **cols) -> "ConnTable":
+        """Copy numpy arrays (any integer dtype of the column's width) into the named columns."""
+        for name, a in cols.items():
+            t = getattr(self, name)
+            a = np.ascontiguousarray(a)
+            t.copy_(torch.from_numpy(a.view(f"i{a.dtype.itemsize}" if t.dtype != torch.uint8 else np.uint8)))
+        return self
+
+    def to(self, device) -> "ConnTable":
+        """A copy of every column and of the index on `device` (the index is valid on either side)."""
+        mv = lambda t: None if t is None else t.to(device, copy=True)  # noqa: E731
+        return ConnTable(self.capacity, self.by_id, *[mv(getattr(self, name)) for name, _, _ in _CONN_COLUMNS],
+                         mv(self.index))
+
+    def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
+        """rsk_conn_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
+        table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
+        if (codec is None) != (self.index.device.type == "cpu"):
+            raise RskError("ConnTable.rebuild: a device table takes its Codec, a cpu table none")
+        if codec is None:
+            _check(lib().rsk_conn_index_build_host(ctypes.byref(self.abi()), _ptr(n_dup), 1),
+                   "rsk_conn_index_build_host")
+        else:
+            codec.conn_index_build(self, n_dup=n_dup, stream=stream)
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def conn_resolve_host(tab: ConnTable, status: np.ndarray, conn_key: np.ndarray, cmd: np.ndarray | None = None,
+                      id: np.ndarray | None = None, nthreads: int = 1):
+    """rsk_conn_resolve_host on a "cpu" ConnTable and numpy columns (no GPU): -> (conn uint32 [n], hit
+    uint8 [n], miss int8 [n], n_miss)."""
+    n = len(status)
+    c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
+    status, conn_key, cmd, id = c(status, np.int8), c(conn_key, np.uint64), c(cmd, np.uint8), c(id, np.uint8)
+    conn, hit, miss = np.full(max(n, 1), 0xEEEEEEEE, np.uint32), np.full(max(n, 1), 0xEE, np.uint8), np.full(max(n, 1), 0x55, np.int8)
+    nm = np.full(1, 0xFFFFFFFF, np.uint32)
+    rin = _abi.ConnResolveIn(_np_ptr(status), _np_ptr(cmd), _np_ptr(id), _np_ptr(conn_key))
+    rout = _abi.ConnResolveOut(_np_ptr(conn), _np_ptr(hit), _np_ptr(miss), _np_ptr(nm))
+    rc = lib().rsk_conn_resolve_host(ctypes.byref(tab.abi()), n, ctypes.byref(rin), ctypes.byref(rout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conn_resolve_host failed: rc={rc}")
+    return conn[:n], hit[:n], miss[:n], int(nm[0])
+
+
+def conn_expand_host(tab: ConnTable, conn: np.ndarray, nthreads: int = 1):
+    """rsk_conn_expand_host on a "cpu" ConnTable (no GPU): -> (dict of the columns src, dst, sp, dp, ack,
+    flag, conn_key, ok and, for a by_id table, id [n * 8]; n_bad)."""
+    n = len(conn)
+    conn = np.ascontiguousarray(conn, np.uint32)
+    m = max(n, 1)
+    o = {"src": np.full(m, 0xEEEEEEEE, np.uint32), "dst": np.full(m, 0xEEEEEEEE, np.uint32),
+         "sp": np.full(m, 0xEEEE, np.uint16), "dp": np.full(m, 0xEEEE, np.uint16),
+         "ack": np.full(m, 0xEEEEEEEE, np.uint32), "flag": np.full(m, 0xEE, np.uint8),
+         "conn_key": np.full(m, 0xEE, np.uint64), "id": np.full(8 * m, 0xEE, np.uint8) if tab.by_id else None,
+         "ok": np.full(m, 0xEE, np.uint8)}
+    nb = np.full(1, 0xFFFFFFFF, np.uint32)
+    eout = _abi.ConnExpandOut(*[_np_ptr(o[k]) for k in ("src", "dst", "sp", "dp", "ack", "flag", "conn_key", "id", "ok")],
+                              _np_ptr(nb))
+    rc = lib().rsk_conn_expand_host(ctypes.byref(tab.abi()), n, _np_ptr(conn), ctypes.byref(eout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conn_expand_host failed: rc={rc}")
+    return {k: (v[:8 * n] if k == "id" else v[:n]) for k, v in o.items() if v is not None}, int(nb[0])
+
+
 @dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
@@ -591,6 +703,36 @@ class Codec:
         vout = _abi.VerifyOut(_ptr(csum), _ptr(status_out), _ptr(n_bad))
         _check(lib().rsk_verify_wire_batch(self._ctx, n, ctypes.byref(vin), datalink, ctypes.byref(vout),
                                            _stream(stream)), "rsk_verify_wire_batch")
+
+    def conn_index_build(self, tab: "ConnTable", n_dup=None, stream=None) -> None:
+        """rsk_conn_index_build: rebuild tab.index from its state, conn_key (and id) columns; n_dup [1]
+        gets the LIVE rows that lost their key to a lower row."""
+        _check(lib().rsk_conn_index_build(self._ctx, ctypes.byref(tab.abi()), _ptr(n_dup), _stream(stream)),
+               "rsk_conn_index_build")
+
+    def conn_resolve_batch(self, tab: "ConnTable", status, conn_key, conn, cmd=None, id=None, hit=None, miss=None,
+                           n_miss=None, stream=None) -> None:
+        """INetGroup::Input's lookup for n decoded packets (rsk_conn_resolve_batch): conn[i] = the row of
+        packet i's connKey (with a by_id table: of its (IdBuf, connKey)) or CONN_NONE; looked up iff
+        status[i] == RECV_VALID and cmd[i] == CMD_DATA (cmd None: all DATA).  hit[i] = 1 iff found (the
+        `delivered` of tcp_recv_ack_batch); miss is a status column of the looked-up packets that were not
+        found (feed it to demux_batch for the distinct missing keys), n_miss [1] their number."""
+        n = status.numel()
+        rin = _abi.ConnResolveIn(_ptr(status), _ptr(cmd), _ptr(id), _ptr(conn_key))
+        rout = _abi.ConnResolveOut(_ptr(conn), _ptr(hit), _ptr(miss), _ptr(n_miss))
+        _check(lib().rsk_conn_resolve_batch(self._ctx, ctypes.byref(tab.abi()), n, ctypes.byref(rin),
+                                            ctypes.byref(rout), _stream(stream)), "rsk_conn_resolve_batch")
+
+    def conn_expand_batch(self, tab: "ConnTable", conn, ok, src=None, dst=None, sp=None, dp=None, ack=None, flag=None,
+                          conn_key=None, id=None, n_bad=None, stream=None) -> None:
+        """INetConn::Output's TcpInfo for n packets to send (rsk_conn_expand_batch): every given column gets
+        row conn[i]'s value -- the columns output_wire_batch takes -- or zero with ok[i] = 0 when the row is
+        out of range or not LIVE | ALIVE; n_bad [1] counts those."""
+        n = conn.numel()
+        eout = _abi.ConnExpandOut(_ptr(src), _ptr(dst), _ptr(sp), _ptr(dp), _ptr(ack), _ptr(flag), _ptr(conn_key),
+                                  _ptr(id), _ptr(ok), _ptr(n_bad))
+        _check(lib().rsk_conn_expand_batch(self._ctx, ctypes.byref(tab.abi()), n, _ptr(conn), ctypes.byref(eout),
+                                           _stream(stream)), "rsk_conn_expand_batch")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

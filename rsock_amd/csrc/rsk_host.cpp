@@ -1,8 +1,9 @@
 // rsk_host.cpp — host-side batch helpers of the header-only path (include/rsk_codec.h): staging
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
-// (rsk_deliver_host) and of the checksum verification (rsk_verify_wire_host); the single-frame slot
-// staging, the capture filter's text form and the connection keys.  Pure host code (no HIP calls).
+// (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
+// (rsk_conn_*_host); the single-frame slot staging, the capture filter's text form and the connection
+// keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
 #include <string>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rsk_codec.h"
+#include "rsk_conn.h"
 
 namespace {
 
@@ -164,6 +166,125 @@ extern "C" int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int dat
             o.csum[i] = (uint8_t)f;
             if (o.status_out) o.status_out[i] = bad ? (int8_t)RSK_RECV_DROP : st;
             nb += bad;
+        }
+        bt->fetch_add(nb, std::memory_order_relaxed);
+    });
+    if (out->n_bad) *out->n_bad = bad_total.load();
+    return RSK_OK;
+}
+
+// ---- connection table (rsk_conn_table): the host twins; hash and probe rule in rsk_conn.h -----------
+namespace {
+
+uint64_t load64(const uint8_t *p) {
+    uint64_t v;
+    std::memcpy(&v, p, 8);
+    return v;
+}
+
+struct HostConnTab {
+    const rsk_conn_table *t;
+    uint32_t entry(uint32_t s) const { return t->index[s]; }
+    uint64_t key(uint32_t row) const { return t->conn_key[row]; }
+    uint64_t id(uint32_t row) const { return load64(t->id + 8ull * row); }
+};
+
+bool conn_tab_ok(const rsk_conn_table *t) {
+    return t && !(t->flags & ~RSK_CONN_BY_ID) && t->capacity >= 1u && t->capacity <= RSK_CONN_MAX_ROWS;
+}
+// what a lookup reads
+bool conn_tab_lookup_ok(const rsk_conn_table *t) {
+    return conn_tab_ok(t) && t->conn_key && t->index && (!(t->flags & RSK_CONN_BY_ID) || t->id);
+}
+
+}  // namespace
+
+extern "C" uint64_t rsk_conn_index_bytes(uint32_t capacity, uint32_t flags) {
+    if ((flags & ~RSK_CONN_BY_ID) || capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    return 4ull * rsk::conn_slots(capacity);
+}
+
+// Rows in increasing order, so the first row of a key takes its entry and every later one is a duplicate.
+extern "C" int rsk_conn_index_build_host(const rsk_conn_table *t, uint32_t *n_dup, int /*nthreads*/) {
+    if (!conn_tab_lookup_ok(t) || !t->state) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(t->index) & 15u) return RSK_EINVAL;
+    const uint32_t slots = rsk::conn_slots(t->capacity);
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    const HostConnTab h{t};
+    std::memset(t->index, 0xFF, 4ull * slots);
+    uint32_t dup = 0;
+    for (uint32_t r = 0; r < t->capacity; ++r) {
+        if (!(t->state[r] & RSK_CONN_LIVE)) continue;
+        const uint64_t key = h.key(r), id = by_id ? h.id(r) : 0ull;
+        for (uint32_t s = rsk::conn_home(key, id, slots);; s = rsk::conn_next(s, slots)) {
+            const uint32_t e = t->index[s];
+            if (e == rsk::kConnEmpty) { t->index[s] = r; break; }
+            if (h.key(e) == key && (!by_id || h.id(e) == id)) { ++dup; break; }
+        }
+    }
+    if (n_dup) *n_dup = dup;
+    return RSK_OK;
+}
+
+extern "C" int rsk_conn_resolve_host(const rsk_conn_table *t, uint32_t n, const rsk_conn_resolve_in *in,
+                                     const rsk_conn_resolve_out *out, int nthreads) {
+    if (!in || !out || !conn_tab_lookup_ok(t)) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    if (n && (!in->status || !in->conn_key || !out->conn || (by_id && !in->id))) return RSK_EINVAL;
+    std::atomic<uint32_t> miss_total{0};
+    std::atomic<uint32_t> *mt = &miss_total;
+    const rsk_conn_resolve_in a = *in;
+    const rsk_conn_resolve_out o = *out;
+    const HostConnTab h{t};
+    const uint32_t cap = t->capacity;
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        uint32_t nm = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const bool look = a.status[i] == RSK_RECV_VALID && (!a.cmd || a.cmd[i] == RSK_CMD_DATA);
+            uint32_t row = RSK_CONN_NONE;
+            if (look) row = rsk::conn_lookup(h, cap, by_id, a.conn_key[i], by_id ? load64(a.id + 8ull * i) : 0ull);
+            const bool miss = look && row == RSK_CONN_NONE;
+            o.conn[i] = row;
+            if (o.hit) o.hit[i] = row != RSK_CONN_NONE;
+            if (o.miss) o.miss[i] = miss ? (int8_t)RSK_RECV_VALID : (int8_t)RSK_RECV_DROP;
+            nm += miss;
+        }
+        mt->fetch_add(nm, std::memory_order_relaxed);
+    });
+    if (out->n_miss) *out->n_miss = miss_total.load();
+    return RSK_OK;
+}
+
+extern "C" int rsk_conn_expand_host(const rsk_conn_table *t, uint32_t n, const uint32_t *conn,
+                                    const rsk_conn_expand_out *out, int nthreads) {
+    if (!out || !conn_tab_ok(t) || !t->state) return RSK_EINVAL;
+    if ((out->src && !t->src) || (out->dst && !t->dst) || (out->sp && !t->sp) || (out->dp && !t->dp) ||
+        (out->ack && !t->ack) || (out->flag && !t->flag) || (out->conn_key && !t->conn_key) || (out->id && !t->id))
+        return RSK_EINVAL;
+    if (n && (!conn || !out->ok)) return RSK_EINVAL;
+    std::atomic<uint32_t> bad_total{0};
+    std::atomic<uint32_t> *bt = &bad_total;
+    const rsk_conn_expand_out o = *out;
+    const rsk_conn_table tab = *t;
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        constexpr uint8_t kUp = RSK_CONN_LIVE | RSK_CONN_ALIVE;
+        uint32_t nb = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t r = conn[i];
+            const bool ok = r < tab.capacity && (tab.state[r] & kUp) == kUp;
+            if (o.src) o.src[i] = ok ? tab.src[r] : 0u;
+            if (o.dst) o.dst[i] = ok ? tab.dst[r] : 0u;
+            if (o.sp) o.sp[i] = ok ? tab.sp[r] : (uint16_t)0;
+            if (o.dp) o.dp[i] = ok ? tab.dp[r] : (uint16_t)0;
+            if (o.ack) o.ack[i] = ok ? tab.ack[r] : 0u;
+            if (o.flag) o.flag[i] = ok ? tab.flag[r] : (uint8_t)0;
+            if (o.conn_key) o.conn_key[i] = ok ? tab.conn_key[r] : 0ull;
+            if (o.id) {
+                if (ok) std::memcpy(o.id + 8ull * i, tab.id + 8ull * r, 8);
+                else std::memset(o.id + 8ull * i, 0, 8);
+            }
+            o.ok[i] = ok;
+            nb += !ok;
         }
         bt->fetch_add(nb, std::memory_order_relaxed);
     });

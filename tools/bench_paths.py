@@ -3,7 +3,9 @@
 process): encode (framing), encode_wire RAW4 / Ethernet (framing + IPv4/TCP build + checksums),
 decode (verify + compaction), parse_decode (pcap parse of the Ethernet wire packets + verify), ...,
 deliver / deliver_demux / deliver_plan (the VALID payloads packed in valid_idx / demux order; offsets only),
-verify_wire_eth / verify_wire_raw4 (IPv4 + TCP checksum check of the wire packets built above).
+verify_wire_eth / verify_wire_raw4 (IPv4 + TCP checksum check of the wire packets built above),
+conn_resolve / conn_resolve_64conn / conn_resolve_miss / conn_expand (the connection table: the decoded
+batch against its own connKeys, 64 connections, half of the keys absent; the send side's gather).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -245,6 +247,54 @@ def main():
         for grid in (2048, 8192, 65536):
             ops[f"dense_read@{grid}"] = lambda grid=grid: hp.probe_run(1, wiree.data_ptr(), ysink.data_ptr(),
                                                                        vf_bytes["eth"], grid, s.cuda_stream)
+    # connection table (rsk_conn_resolve_batch / rsk_conn_expand_batch): the decoded batch against a table
+    # of its own connKeys, the 64-connection batch of demux_64conn, half of the keys absent, and the send
+    # side's gather over 64 connections
+    def conn_table(keys):
+        t = rc.ConnTable.alloc(max(int(keys.numel()), 1), dev)
+        t.conn_key[:keys.numel()] = keys
+        t.state[:keys.numel()] = A.CONN_LIVE | A.CONN_ALIVE
+        for col in (t.src, t.dst, t.sp, t.dp, t.seq, t.ack):
+            col.copy_(torch.randint(0, 2**15, (t.capacity,), device=dev, generator=gk, dtype=torch.int64).to(col.dtype))
+        t.flag.fill_(0x18)
+        t.rebuild(cx, stream=s)
+        return t
+
+    own_keys = torch.unique(ddec.conn_key[ddec.status == 1])
+    tab_own, tab_half, tab_64 = conn_table(own_keys), conn_table(own_keys[::2]), conn_table(torch.unique(k_key))
+    r_conn, r_hit = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    r_nm = torch.empty(1, dtype=torch.int32, device=dev)
+    ops["conn_resolve"] = lambda: cx.conn_resolve_batch(tab_own, ddec.status, ddec.conn_key, r_conn, cmd=ddec.cmd,
+                                                        hit=r_hit, stream=s)
+    ops["conn_resolve_64conn"] = lambda: cx.conn_resolve_batch(tab_64, k_st, k_key, r_conn, cmd=k_cmd, hit=r_hit,
+                                                               stream=s)
+    ops["conn_resolve_miss"] = lambda: cx.conn_resolve_batch(tab_half, ddec.status, ddec.conn_key, r_conn,
+                                                             cmd=ddec.cmd, hit=r_hit, n_miss=r_nm, stream=s)
+    x_cols = {"src": torch.int32, "dst": torch.int32, "sp": torch.int16, "dp": torch.int16, "ack": torch.int32,
+              "flag": torch.uint8, "conn_key": torch.int64}
+    x_out = {k: torch.empty(n, dtype=dt, device=dev) for k, dt in x_cols.items()}
+    x_ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    ops["conn_expand"] = lambda: cx.conn_expand_batch(tab_64, conn64, x_ok, stream=s, **x_out)
+    looked = int(((ddec.status == 1) & (ddec.cmd == 0)).sum().item())
+    for k in ("conn_resolve", "conn_resolve_64conn", "conn_resolve_miss", "conn_expand"):
+        ops[k]()
+    torch.cuda.synchronize()
+    assert int(r_nm.item()) > 0 and bool((x_ok == 1).all())
+    ops["conn_resolve"]()
+    torch.cuda.synchronize()
+    assert int(r_hit.sum().item()) == looked
+    conn_tables = {"conn_resolve": tab_own.capacity, "conn_resolve_miss": tab_half.capacity,
+                   "conn_resolve_64conn": tab_64.capacity, "conn_expand": tab_64.capacity,
+                   "conn_resolve_miss_packets": int(r_nm.item())}
+    # status, cmd, connKey read; conn, hit written.  conn read; the seven columns and ok written
+    conn_alg = {"conn_resolve": 1 + 1 + 8 + 4 + 1, "conn_expand": 4 + 4 + 4 + 2 + 2 + 4 + 1 + 8 + 1}
+    if args.read_yardstick:
+        # the dense 16-B read of the same byte counts (the wire arena's first bytes)
+        for name, per in (("resolve", conn_alg["conn_resolve"]), ("expand", conn_alg["conn_expand"])):
+            assert n * per <= wiree.numel()
+            for grid in (2048, 8192, 65536):
+                ops[f"dense_read_{name}@{grid}"] = lambda grid=grid, per=per: hp.probe_run(
+                    1, wiree.data_ptr(), ysink.data_ptr(), n * per, grid, s.cuda_stream)
     nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -294,6 +344,10 @@ def main():
     # verify: link header + IPv4 total length read, one flag byte written
     alg.update({"verify_wire_eth": vf_bytes["eth"] / n + 1, "verify_wire_raw4": vf_bytes["raw4"] / n + 1})
     alg.update({k: vf_bytes["eth"] / n for k in ops if k.startswith("dense_read@")})
+    alg.update({k: conn_alg["conn_resolve"] for k in ("conn_resolve", "conn_resolve_64conn", "conn_resolve_miss")})
+    alg["conn_expand"] = conn_alg["conn_expand"]
+    alg.update({k: conn_alg["conn_resolve"] for k in ops if k.startswith("dense_read_resolve@")})
+    alg.update({k: conn_alg["conn_expand"] for k in ops if k.startswith("dense_read_expand@")})
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -318,6 +372,15 @@ def main():
         for k in ("verify_wire_eth", "verify_wire_raw4"):
             if k in out:
                 res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dread), 3)
+    if any(k.startswith("conn_") for k in out):
+        res["conn_table_rows"] = conn_tables
+    for name, rows in (("resolve", ("conn_resolve", "conn_resolve_64conn", "conn_resolve_miss")), ("expand", ("conn_expand",))):
+        dr = [v["ms"] for k, v in out.items() if k.startswith(f"dense_read_{name}@")]
+        if dr:
+            res[f"dense_read_{name}_ms"] = min(dr)
+            for k in rows:
+                if k in out:
+                    res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dr), 3)
     print(json.dumps(res))
 
 
