@@ -43,6 +43,12 @@
  *                            (conn/FakeTcp.cpp:14-50) to RawTcp::Output as the packet's addresses, ports,
  *                            ack and flag
  *   rsk_conn_table        <- INetGroup's mConnMap and the TcpInfo mInfo of each FakeTcp in it
+ *   rsk_control_batch     <- IAppGroup::Input's control branches (conn/IAppGroup.cpp:76-96), ConnReset::Input
+ *                            (callbacks/ConnReset.cpp:43-90), NetConnKeepAlive::Input
+ *                            (callbacks/NetConnKeepAlive.cpp:37-98), IAppGroup::ProcessTcpFinOrRst
+ *                            (conn/IAppGroup.cpp:103-116)
+ *   rsk_keepalive_flush   <- NetConnKeepAlive::OnFlush / canSendRequest (callbacks/NetConnKeepAlive.cpp:110-145,
+ *                            :168-178)
  */
 #ifndef RSK_CODEC_H
 #define RSK_CODEC_H
@@ -175,7 +181,8 @@ int rsk_set_encode_path(rsk_ctx *ctx, int path);
  * kernels read is the immutable key schedule and tag table (and the tag mode, passed by value).
  *
  * Pre-size the scratch of `stream` (rsk_reserve: the legacy default stream, NULL) for batches of up
- * to n packets: the compaction state and, for n >= 16384, the header records of the two-pass encode
+ * to n packets: the compaction state, the tile sums of rsk_deliver_batch and the tile counts of
+ * rsk_control_batch / rsk_keepalive_flush (8 B per 1024 / 2048 packets), and, for n >= 16384, the header records of the two-pass encode
  * and wire build (max(40 n + 24, 96 min(n, 2^20)) bytes: 32-B records and the output-stationary
  * copy's block map) -- only for a context that encodes: one held to RSK_ENC_PATH_TWO_PASS, or an AUTO
  * context that has already run an rsk_encode_batch call (so a decode- or demux-only context pays
@@ -633,7 +640,7 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
 
 typedef struct rsk_conn_table {  /* device pointers, caller-owned, `capacity` rows */
     uint32_t capacity, flags;    /* capacity in [1, RSK_CONN_MAX_ROWS]; flags: RSK_CONN_BY_ID or 0   */
-    const uint8_t  *state;       /* [C] RSK_CONN_LIVE | RSK_CONN_ALIVE bits */
+    const uint8_t  *state;       /* [C] RSK_CONN_LIVE | RSK_CONN_ALIVE | RSK_CONN_NEW bits */
     const uint64_t *conn_key;    /* [C] INetConn::mIntKey */
     const uint8_t  *id;          /* [C*8], 8-B aligned; BY_ID only, else may be NULL */
     const uint32_t *src, *dst;   /* [C] TcpInfo as stored */
@@ -715,6 +722,163 @@ int rsk_conn_resolve_host(const rsk_conn_table *tab, uint32_t n, const rsk_conn_
                           const rsk_conn_resolve_out *out, int nthreads);
 int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *conn,
                          const rsk_conn_expand_out *out, int nthreads);
+
+/* ---- control packets and the keepalive timer on the connection table ------------------------------ */
+/* Every packet that is not DATA is the reference's per packet: IAppGroup::Input branches on cmd
+ * (conn/IAppGroup.cpp:76-96), ConnReset::Input (callbacks/ConnReset.cpp:43-90) and
+ * NetConnKeepAlive::Input (callbacks/NetConnKeepAlive.cpp:37-98) read a 4- or 8-byte body, look the
+ * body's key up in mConnMap and answer, report the conn or clear a pending request; a FIN / RST packet
+ * (RSK_RECV_CLOSE) reaches IAppGroup::ProcessTcpFinOrRst (conn/IAppGroup.cpp:103-116).  The state they
+ * touch is the table above, and NetConnKeepAlive::OnFlush (:110-145) is a pass over its rows.
+ *   receive  parse_decode -> verify -> resolve -> rsk_control_batch -> (the host picks a conn per
+ *            message) -> expand -> send_seq -> rsk_encode_wire_batch
+ *   timer    rsk_keepalive_flush -> the same message columns, and the rows that timed out
+ *
+ * rsk_control_batch classifies packet i, reads the body of a control packet at
+ * arena + base_off[i] + inner_off[i] + pay_off[i], and looks its key up by the resolve's rule: the LIVE
+ * row found by the index, whether or not ALIVE; with RSK_CONN_BY_ID the key is the pair (id[i], arg).
+ *   kind              when                                         arg                      conn
+ *   RSK_CTL_NONE      not VALID (and no examined CLOSE), cmd DATA  0                        NONE
+ *   RSK_CTL_CONV_RST  cmd 1, pay_len >= 4                          LE32 of body[0..4)       NONE (the lookup by
+ *                                             BuildConvKey(dst, conv), ConnReset.cpp:67-77, stays above this level)
+ *   RSK_CTL_NETCONN_RST cmd 2, pay_len >= 8                        LE64 of body[0..8)       row (OnRecvNetConnRst ->
+ *                                             NotifyErr(ERR_FIN_RST), :79-90) or NONE
+ *   RSK_CTL_KA_REQ    cmd 3, pay_len >= 8                          LE64                     row: answered with
+ *                                             KEEP_ALIVE_RESP; NONE: answered with NETCONN_RST (:41-48)
+ *   RSK_CTL_KA_RESP   cmd 4, pay_len >= 8                          LE64                     row: RemoveRequest; NONE
+ *   RSK_CTL_TCP_CLOSE status RSK_RECV_CLOSE, tcp_sp / tcp_dp       rsk_key_for_tcp(sp, dp)  row or NONE
+ *                     given, table without BY_ID                   (KeyForConnInfo)
+ *   RSK_CTL_SHORT     cmd 1-4, body shorter than above (the reference returns -1)   0       NONE
+ *   RSK_CTL_UNKNOWN   VALID, cmd > 4                               0                        NONE
+ * A CLOSE packet on a BY_ID table, or without the port columns, is RSK_CTL_NONE
+ * (ServerGroup::OnTcpFinOrRst walks every SubGroup in map order: the host's).  Only the body bytes
+ * [0, 4) / [0, 8) are read: no 16-B aligned chunk that holds none of them is loaded, and a packet of
+ * kind NONE, SHORT, UNKNOWN or TCP_CLOSE has no frame byte read at all.
+ *
+ * Per-row effects, on caller-owned columns of `capacity` rows (both optional):
+ *   rst_first[r]  the smallest packet index whose kind is NETCONN_RST or TCP_CLOSE and whose conn is r,
+ *                 0xFFFFFFFF when there is none (the call fills the column on the stream, then takes
+ *                 atomicMin);
+ *   ka_tries[r]   (in/out, shared with rsk_keepalive_flush) set to RSK_KA_NONE by any KA_RESP whose conn is r.
+ * SNAPSHOT SEMANTICS -- a deliberate deviation.  Every lookup of a call sees the table as last indexed.
+ * The reference walks the packets one at a time: after a NETCONN_RST of key K that hit (and whose error
+ * handler removed the conn), its later packets see K gone.  A packet at or before its row's rst_first
+ * gets what the reference gives it; rst_first is what lets a caller redo the tail for the few rows
+ * concerned.
+ *
+ * Messages to send (rsk_ctl_msgs): an order-stable compacted list, in packet order, of
+ *   - one message per KA_REQ: cmd KEEP_ALIVE_RESP, avoid_key 0 when it hit; cmd NETCONN_RST,
+ *     avoid_key = arg when it missed; body = arg in both;
+ *   - with in->miss given (the resolve's miss column), one NETCONN_RST with body = avoid_key =
+ *     conn_key[i] for every other packet with miss[i] == RSK_RECV_VALID: the per-packet SendNetConnRst
+ *     of conn/IAppGroup.cpp:84-86 (the demux-based "one reset per key" recipe above stays available).
+ * Entry k: cmd[k]; body[k] (to be sent as 8 LE bytes); id[8k .. 8k+8) the packet's IdBuf (zeros without an
+ * id column); src[k] the packet index; avoid_key[k] doSend's keyOfConnToReset, the conn the reset must
+ * not travel on (0 = none, as the reference); pay_off[k] = 8k and pay_len[k] = 8 -- so the columns are an
+ * rsk_encode_in as they stand with `body` as the payload arena; the conn the caller picks supplies
+ * conn_key through rsk_conn_expand_batch, and conv is the caller's (the receiver branches on cmd before
+ * it reads conv).  Every array holds n entries and is optional; n_msg is required when any array is
+ * given.  *n_msg and *n_ctl (the packets whose kind is not NONE) are written, not accumulated.
+ *
+ * Three launches on `stream`, a linear chain: per-tile counts, one block that scans them, and the pass
+ * that classifies, gathers, probes and writes; no block waits on another.  Scratch: 8 B per 2048 packets
+ * per stream, sized by rsk_reserve_stream, so a captured call replays.  n == 0 zeroes the given counts
+ * and fills a given rst_first.  RSK_EINVAL: a NULL ctx, tab, in or out; a table a lookup cannot use (as
+ * rsk_conn_resolve_batch); with n > 0 a NULL status, cmd, arena, base_off, pay_off or pay_len; id
+ * missing with BY_ID; an id column (the table's with BY_ID, or in->id) that is not 8-B aligned; tcp_sp
+ * and tcp_dp not both set or both NULL; miss without conn_key; a message array without n_msg;
+ * n > RSK_MAX_BATCH. */
+#define RSK_CONN_NEW 0x4u /* state bit: INetConn::mNew, set at creation and cleared by the host at the
+                             conn's first send (rsk_keepalive_flush skips such a row) */
+#define RSK_CTL_NONE        0
+#define RSK_CTL_CONV_RST    1
+#define RSK_CTL_NETCONN_RST 2
+#define RSK_CTL_KA_REQ      3
+#define RSK_CTL_KA_RESP     4
+#define RSK_CTL_TCP_CLOSE   5
+#define RSK_CTL_SHORT       6
+#define RSK_CTL_UNKNOWN     7
+#define RSK_KA_NONE 0xFFu               /* ka_tries: the row has no entry in mReqMap */
+#define RSK_KA_REQUEST_DELAY_MS 15000u  /* NetConnKeepAlive::REQUEST_DELAY */
+#define RSK_KA_MAX_RETRY 3u             /* NetConnKeepAlive::MAX_RETRY */
+
+typedef struct rsk_control_in {
+    const int8_t   *status;    /* [n] dec->status */
+    const uint8_t  *cmd;       /* [n] dec->cmd */
+    const uint8_t  *id;        /* [n*8] dec->id, 8-B aligned; required with BY_ID, else only copied to the messages */
+    const uint64_t *conn_key;  /* [n] dec->conn_key (EncHead's); only read for the miss option */
+    const uint16_t *pay_off;   /* [n] dec->pay_off */
+    const uint16_t *pay_len;   /* [n] dec->pay_len */
+    const uint8_t  *arena;     /* the bytes the frames lie in, as rsk_deliver_in */
+    const uint64_t *base_off;  /* [n] */
+    const uint16_t *inner_off; /* [n] or NULL = 0 */
+    const uint16_t *tcp_sp, *tcp_dp; /* [n] the parse's TcpInfo ports, or both NULL */
+    const int8_t   *miss;      /* [n] the resolve's miss column, or NULL */
+} rsk_control_in;
+typedef struct rsk_ctl_msgs {  /* every array optional; n_msg required when any is given */
+    uint8_t  *cmd;        /* [m] */
+    uint64_t *body;       /* [m] */
+    uint8_t  *id;         /* [m*8], 8-B aligned */
+    uint32_t *src;        /* [m] packet index (rsk_control_batch) or row (rsk_keepalive_flush) */
+    uint64_t *avoid_key;  /* [m] */
+    uint64_t *pay_off;    /* [m] 8k */
+    uint16_t *pay_len;    /* [m] 8 */
+    uint32_t *n_msg;      /* [1] */
+} rsk_ctl_msgs;
+typedef struct rsk_control_out {  /* every output optional */
+    uint8_t  *kind;      /* [n] RSK_CTL_* */
+    uint64_t *arg;       /* [n] */
+    uint32_t *conn;      /* [n] row, or RSK_CONN_NONE */
+    uint32_t *n_ctl;     /* [1] */
+    uint32_t *rst_first; /* [capacity] */
+    uint8_t  *ka_tries;  /* [capacity] in/out */
+    rsk_ctl_msgs msgs;   /* m = n */
+} rsk_control_out;
+int rsk_control_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, const rsk_control_in *in,
+                      const rsk_control_out *out, void *stream);
+
+/* NetConnKeepAlive::OnFlush (callbacks/NetConnKeepAlive.cpp:110-145) as one pass over the rows.
+ * ka_tries[r] is the row's entry of mReqMap, RSK_KA_NONE when it has none.  Per row r, in this order:
+ *   1. r is not LIVE: ka_tries[r] = RSK_KA_NONE (removeInvalidRequest); done with r.  With online == 0
+ *      (mRouteObserver->Online() false, :111-114) nothing else runs for any row.
+ *   2. can = !(state & RSK_CONN_NEW) && now_ms > est && (int32_t)(uint32_t)(now_ms - est) >=
+ *      (int32_t)request_delay_ms, est = established_ms[r]: canSendRequest's `int df` (:168-178), its
+ *      truncation of the 64-bit difference included, reproduced as-is.
+ *   3. If can: had = tries != NONE; tries = had ? tries + 1 : 0; a KEEP_ALIVE_REQ is emitted iff !had or
+ *      tries < max_retry.
+ *   4. If tries != NONE and tries >= max_retry: tries = NONE and r is appended to dead_rows
+ *      (onNetConnDead -> NotifyErr(ERR_TIMEOUT)).
+ * Both lists are in row order, their counts written, not accumulated.  A message has cmd
+ * KEEP_ALIVE_REQ, body = the row's conn_key, id = the row's IdBuf (zeros for a table without an id
+ * column), src = r, avoid_key 0, pay_off 8k, pay_len 8; the arrays hold `capacity` entries.  The table's
+ * state stays read-only: the host clears ALIVE for the dead rows and rebuilds when it removes them.  No
+ * index is read.  The launches and the scratch are rsk_control_batch's (8 B per 1024 rows).
+ * RSK_EINVAL: a NULL ctx, tab, ka, out, tab->state, tab->conn_key, ka_tries or established_ms; unknown
+ * table flags or a capacity outside [1, RSK_CONN_MAX_ROWS]; max_retry outside [1, 254]; a message array
+ * without n_msg, dead_rows without n_dead; an id column (the table's or msgs.id) that is not 8-B aligned
+ * when msgs.id is given. */
+typedef struct rsk_keepalive {
+    uint8_t        *ka_tries;        /* [C] in/out */
+    const uint64_t *established_ms;  /* [C] INetConn::EstablishedTimeStampMs() */
+    uint64_t        now_ms;          /* OnFlush's timestamp */
+    uint32_t        request_delay_ms;/* RSK_KA_REQUEST_DELAY_MS */
+    uint32_t        max_retry;       /* RSK_KA_MAX_RETRY */
+    uint32_t        online;          /* 0: only step 1 runs */
+} rsk_keepalive;
+typedef struct rsk_keepalive_out {
+    rsk_ctl_msgs msgs;     /* m = capacity */
+    uint32_t *dead_rows;   /* [C] optional */
+    uint32_t *n_dead;      /* [1] required with dead_rows */
+} rsk_keepalive_out;
+int rsk_keepalive_flush(rsk_ctx *ctx, const rsk_conn_table *tab, const rsk_keepalive *ka,
+                        const rsk_keepalive_out *out, void *stream);
+
+/* Host twins (host pointers, the same rules and outputs, nthreads as rsk_deliver_host; the IdBuf
+ * columns are read bytewise at any alignment). */
+int rsk_control_host(const rsk_conn_table *tab, uint32_t n, const rsk_control_in *in, const rsk_control_out *out,
+                     int nthreads);
+int rsk_keepalive_flush_host(const rsk_conn_table *tab, const rsk_keepalive *ka, const rsk_keepalive_out *out,
+                             int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

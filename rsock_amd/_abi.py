@@ -46,7 +46,12 @@ VERIFY_MAX_BATCH = 0x1FFFFFE0
 CONN_NONE = 0xFFFFFFFF
 CONN_MAX_ROWS = 1 << 20
 CONN_BY_ID = 0x1
-CONN_LIVE, CONN_ALIVE = 0x1, 0x2
+CONN_LIVE, CONN_ALIVE, CONN_NEW = 0x1, 0x2, 0x4
+(CTL_NONE, CTL_CONV_RST, CTL_NETCONN_RST, CTL_KA_REQ, CTL_KA_RESP, CTL_TCP_CLOSE, CTL_SHORT,
+ CTL_UNKNOWN) = range(8)
+KA_NONE = 0xFF
+KA_REQUEST_DELAY_MS = 15000
+KA_MAX_RETRY = 3
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -161,6 +166,30 @@ class ConnExpandOut(ctypes.Structure):
                 ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
 
 
+class ControlIn(ctypes.Structure):
+    _fields_ = [("status", _vp), ("cmd", _vp), ("id", _vp), ("conn_key", _vp), ("pay_off", _vp), ("pay_len", _vp),
+                ("arena", _vp), ("base_off", _vp), ("inner_off", _vp), ("tcp_sp", _vp), ("tcp_dp", _vp), ("miss", _vp)]
+
+
+class CtlMsgs(ctypes.Structure):
+    _fields_ = [("cmd", _vp), ("body", _vp), ("id", _vp), ("src", _vp), ("avoid_key", _vp), ("pay_off", _vp),
+                ("pay_len", _vp), ("n_msg", _vp)]
+
+
+class ControlOut(ctypes.Structure):
+    _fields_ = [("kind", _vp), ("arg", _vp), ("conn", _vp), ("n_ctl", _vp), ("rst_first", _vp), ("ka_tries", _vp),
+                ("msgs", CtlMsgs)]
+
+
+class Keepalive(ctypes.Structure):
+    _fields_ = [("ka_tries", _vp), ("established_ms", _vp), ("now_ms", ctypes.c_uint64),
+                ("request_delay_ms", ctypes.c_uint32), ("max_retry", ctypes.c_uint32), ("online", ctypes.c_uint32)]
+
+
+class KeepaliveOut(ctypes.Structure):
+    _fields_ = [("msgs", CtlMsgs), ("dead_rows", _vp), ("n_dead", _vp)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -242,6 +271,14 @@ SIGNATURES = [
       ctypes.c_int]),
     ("rsk_conn_expand_host", ctypes.c_int,
      [ctypes.POINTER(ConnTable), ctypes.c_uint32, _vp, ctypes.POINTER(ConnExpandOut), ctypes.c_int]),
+    ("rsk_control_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ControlIn), ctypes.POINTER(ControlOut), _vp]),
+    ("rsk_keepalive_flush", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.POINTER(Keepalive), ctypes.POINTER(KeepaliveOut), _vp]),
+    ("rsk_control_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ControlIn), ctypes.POINTER(ControlOut), ctypes.c_int]),
+    ("rsk_keepalive_flush_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.POINTER(Keepalive), ctypes.POINTER(KeepaliveOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

@@ -398,6 +398,107 @@ def conn_expand_host(tab: ConnTable, conn: np.ndarray, nthreads: int = 1):
     return {k: (v[:8 * n] if k == "id" else v[:n]) for k, v in o.items() if v is not None}, int(nb[0])
 
 
+def _addr(a) -> int | None:
+    """Address of a torch tensor or a numpy array (None stays None)."""
+    if a is None:
+        return None
+    return a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+
+
+_MSG_COLUMNS = (("msg_cmd", torch.uint8, 1), ("msg_body", torch.int64, 1), ("msg_id", torch.uint8, 8),
+                ("msg_src", torch.int32, 1), ("msg_avoid_key", torch.int64, 1), ("msg_pay_off", torch.int64, 1),
+                ("msg_pay_len", torch.int16, 1))
+
+
+@dataclass
+class ControlBuffers:
+    """Outputs of rsk_control_batch for n packets and of rsk_keepalive_flush for a table of `capacity`
+    rows (rsk_control_out, rsk_keepalive_out, rsk_ctl_msgs), on a device or on "cpu" for the host twins;
+    signed storage of the unsigned C types.  kind / arg / conn [n] and n_ctl [1]; rst_first [capacity];
+    the message columns msg_* [m] with n_msg [1] -- an rsk_encode_in as they stand: payload = msg_body
+    viewed as bytes, pay_off = msg_pay_off, pay_len = msg_pay_len, cmd = msg_cmd, id = msg_id;
+    dead_rows [capacity] with n_dead [1].  Any field may be set to None before a call: every output is
+    optional (n_msg is needed with a message column, n_dead with dead_rows)."""
+
+    kind: torch.Tensor | None
+    arg: torch.Tensor | None
+    conn: torch.Tensor | None
+    n_ctl: torch.Tensor | None
+    rst_first: torch.Tensor | None
+    msg_cmd: torch.Tensor | None
+    msg_body: torch.Tensor | None
+    msg_id: torch.Tensor | None
+    msg_src: torch.Tensor | None
+    msg_avoid_key: torch.Tensor | None
+    msg_pay_off: torch.Tensor | None
+    msg_pay_len: torch.Tensor | None
+    n_msg: torch.Tensor | None
+    dead_rows: torch.Tensor | None
+    n_dead: torch.Tensor | None
+
+    @classmethod
+    def alloc(cls, n: int, device, capacity: int = 0, m: int | None = None) -> "ControlBuffers":
+        """For control_batch: alloc(n, device, capacity) (m = n message entries).  For keepalive_flush:
+        alloc(0, device, capacity, m=capacity)."""
+        m = n if m is None else m
+        e = lambda k, dt: torch.empty(k, dtype=dt, device=device)  # noqa: E731
+        return cls(kind=e(n, torch.uint8), arg=e(n, torch.int64), conn=e(n, torch.int32), n_ctl=e(1, torch.int32),
+                   rst_first=e(capacity, torch.int32) if capacity else None,
+                   **{name: e(m * k, dt) for name, dt, k in _MSG_COLUMNS}, n_msg=e(1, torch.int32),
+                   dead_rows=e(capacity, torch.int32) if capacity else None, n_dead=e(1, torch.int32))
+
+    def abi_msgs(self) -> _abi.CtlMsgs:
+        return _abi.CtlMsgs(*[_addr(getattr(self, name)) for name, _, _ in _MSG_COLUMNS], _addr(self.n_msg))
+
+    def abi_control(self, ka_tries=None) -> _abi.ControlOut:
+        return _abi.ControlOut(_addr(self.kind), _addr(self.arg), _addr(self.conn), _addr(self.n_ctl),
+                               _addr(self.rst_first), _addr(ka_tries), self.abi_msgs())
+
+    def abi_flush(self) -> _abi.KeepaliveOut:
+        return _abi.KeepaliveOut(self.abi_msgs(), _addr(self.dead_rows), _addr(self.n_dead))
+
+    def messages(self) -> dict:
+        """The first n_msg entries of the given message columns on the host (numpy, unsigned; id as
+        [n_msg, 8] bytes)."""
+        k = int(self.n_msg.cpu().numpy().view(np.uint32)[0])
+        out = {}
+        for name, dt, w in _MSG_COLUMNS:
+            t = getattr(self, name)
+            if t is not None:
+                a = t[:k * w].cpu().numpy()
+                out[name[4:]] = a.reshape(k, 8) if w == 8 else a.view(f"u{a.dtype.itemsize}")
+        return out
+
+
+def _control_in(status, cmd, pay_off, pay_len, arena, base_off, id, conn_key, inner_off, tcp_sp, tcp_dp,
+                miss) -> _abi.ControlIn:
+    return _abi.ControlIn(_addr(status), _addr(cmd), _addr(id), _addr(conn_key), _addr(pay_off), _addr(pay_len),
+                          _addr(arena), _addr(base_off), _addr(inner_off), _addr(tcp_sp), _addr(tcp_dp), _addr(miss))
+
+
+def control_host(tab: ConnTable, status, cmd, pay_off, pay_len, arena, base_off, out: ControlBuffers, id=None,
+                 conn_key=None, inner_off=None, tcp_sp=None, tcp_dp=None, miss=None, ka_tries=None,
+                 nthreads: int = 1) -> None:
+    """rsk_control_host on a "cpu" ConnTable, with "cpu" tensors or numpy arrays of the C types' widths
+    (no GPU); the arguments of Codec.control_batch."""
+    cin = _control_in(status, cmd, pay_off, pay_len, arena, base_off, id, conn_key, inner_off, tcp_sp, tcp_dp, miss)
+    rc = lib().rsk_control_host(ctypes.byref(tab.abi()), len(status), ctypes.byref(cin),
+                                ctypes.byref(out.abi_control(ka_tries)), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_control_host failed: rc={rc}")
+
+
+def keepalive_flush_host(tab: ConnTable, ka_tries, established_ms, now_ms: int, out: ControlBuffers,
+                         request_delay_ms: int = _abi.KA_REQUEST_DELAY_MS, max_retry: int = _abi.KA_MAX_RETRY,
+                         online: bool = True, nthreads: int = 1) -> None:
+    """rsk_keepalive_flush_host on a "cpu" ConnTable (no GPU); the arguments of Codec.keepalive_flush."""
+    ka = _abi.Keepalive(_addr(ka_tries), _addr(established_ms), now_ms, request_delay_ms, max_retry, int(online))
+    rc = lib().rsk_keepalive_flush_host(ctypes.byref(tab.abi()), ctypes.byref(ka), ctypes.byref(out.abi_flush()),
+                                        nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_keepalive_flush_host failed: rc={rc}")
+
+
 @dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
@@ -733,6 +834,34 @@ class Codec:
                                   _ptr(id), _ptr(ok), _ptr(n_bad))
         _check(lib().rsk_conn_expand_batch(self._ctx, ctypes.byref(tab.abi()), n, _ptr(conn), ctypes.byref(eout),
                                            _stream(stream)), "rsk_conn_expand_batch")
+
+    def control_batch(self, tab: "ConnTable", status, cmd, pay_off, pay_len, arena, base_off, out: "ControlBuffers",
+                      id=None, conn_key=None, inner_off=None, tcp_sp=None, tcp_dp=None, miss=None, ka_tries=None,
+                      stream=None) -> None:
+        """The control branches of IAppGroup::Input, ConnReset::Input, NetConnKeepAlive::Input and
+        IAppGroup::ProcessTcpFinOrRst for n decoded packets (rsk_control_batch): out.kind[i] = CTL_*,
+        out.arg[i] = the key (or conv) in the body at arena + base_off + inner_off + pay_off, out.conn[i]
+        = its LIVE row in `tab` or CONN_NONE.  out.rst_first[r] = the first packet that resets row r;
+        ka_tries[r] (the column keepalive_flush keeps) is cleared by a KEEP_ALIVE_RESP for r.  The
+        messages to send -- a KEEP_ALIVE_RESP or a NETCONN_RST per KEEP_ALIVE_REQ and, with `miss` (the
+        resolve's) and conn_key, a NETCONN_RST per missed DATA packet -- land in out.msg_* in packet
+        order, out.n_msg of them.  tcp_sp / tcp_dp (the parse's ports) make the RECV_CLOSE packets of a
+        table without by_id CTL_TCP_CLOSE.  Lookups see the table as last indexed."""
+        cin = _control_in(status, cmd, pay_off, pay_len, arena, base_off, id, conn_key, inner_off, tcp_sp, tcp_dp, miss)
+        _check(lib().rsk_control_batch(self._ctx, ctypes.byref(tab.abi()), status.numel(), ctypes.byref(cin),
+                                       ctypes.byref(out.abi_control(ka_tries)), _stream(stream)), "rsk_control_batch")
+
+    def keepalive_flush(self, tab: "ConnTable", ka_tries, established_ms, now_ms: int, out: "ControlBuffers",
+                        request_delay_ms: int = _abi.KA_REQUEST_DELAY_MS, max_retry: int = _abi.KA_MAX_RETRY,
+                        online: bool = True, stream=None) -> None:
+        """NetConnKeepAlive::OnFlush as one pass over the rows of `tab` (rsk_keepalive_flush): ka_tries
+        [capacity] (uint8, KA_NONE = no pending request) is advanced in place, the KEEP_ALIVE_REQ messages
+        land in out.msg_* in row order (out.n_msg), the rows that timed out in out.dead_rows
+        (out.n_dead).  established_ms [capacity] and now_ms are milliseconds; a row with CONN_NEW set, or
+        younger than request_delay_ms, sends nothing; online False only purges the rows that are not LIVE."""
+        ka = _abi.Keepalive(_addr(ka_tries), _addr(established_ms), now_ms, request_delay_ms, max_retry, int(online))
+        _check(lib().rsk_keepalive_flush(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(ka),
+                                         ctypes.byref(out.abi_flush()), _stream(stream)), "rsk_keepalive_flush")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

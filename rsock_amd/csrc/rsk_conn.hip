@@ -14,28 +14,21 @@
 // and no host state: a memset node for a given count and one kernel per call.
 #include <hip/hip_runtime.h>
 
-#include "rsk_conn.h"
-#include "rsk_ctx.h"
-#include "rsk_device.h"
+#include "rsk_conn_dev.h"
 
 namespace {
 
+using rsk::DevConnTab;
+using rsk::dev_tab;
 using rsk::gptr;
+using rsk::tab_lookup_ok;
+using rsk::tab_ok;
+using rsk::zero_word;
 
 constexpr unsigned kBlock = 256;  // threads per block
 static_assert((uint64_t)RSK_MAX_BATCH + 8u * kBlock - 1u <= 0xFFFFFFFFull, "the block counts are computed in 32 bits");
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// The table as the kernels read it (rsk_conn.h's conn_lookup takes these three).
-struct DevConnTab {
-    const uint32_t *index;
-    const uint64_t *conn_key;
-    const uint64_t *ids;  // the [C*8] IdBuf bytes, 8-B aligned, one word per row
-    __device__ __forceinline__ uint32_t entry(uint32_t s) const { return gptr(index)[s]; }
-    __device__ __forceinline__ uint64_t key(uint32_t row) const { return gptr(conn_key)[row]; }
-    __device__ __forceinline__ uint64_t id(uint32_t row) const { return gptr(ids)[row]; }
-};
 
 // One atomic per wave for a count of lanes (the word was zeroed on the stream ahead of the launch).
 __device__ __forceinline__ void wave_count(uint32_t *word, bool mine) {
@@ -192,24 +185,6 @@ __global__ __launch_bounds__(kBlock) void k_conn_expand(ExpandArgs a) {
         gptr(a.o.ok)[i] = ok;
     }
     if (a.o.n_bad) wave_count(a.o.n_bad, live && !ok);
-}
-
-bool tab_ok(const rsk_conn_table *t) {
-    return t && !(t->flags & ~RSK_CONN_BY_ID) && t->capacity >= 1u && t->capacity <= RSK_CONN_MAX_ROWS;
-}
-bool tab_lookup_ok(const rsk_conn_table *t) {
-    return tab_ok(t) && t->conn_key && t->index && (!(t->flags & RSK_CONN_BY_ID) || t->id);
-}
-DevConnTab dev_tab(const rsk_conn_table *t) {
-    return DevConnTab{t->index, t->conn_key, reinterpret_cast<const uint64_t *>(t->id)};
-}
-
-// Zero a given device count on the stream ahead of the kernel that adds to it.
-int zero_word(uint32_t *word, hipStream_t s) {
-    if (!word) return RSK_OK;
-    hipError_t e = hipMemsetAsync(word, 0, 4, s);
-    if (e != hipSuccess) { rsk::set_error("hipMemsetAsync", e); return RSK_EDEVICE; }
-    return RSK_OK;
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 // Internal (not installed): the rsk_ctx handle and host helpers shared by the librsk translation
-// units (rsk_kernels.hip: codec; rsk_demux.hip: receive demux; rsk_deliver.hip: payload delivery).
+// units (rsk_kernels.hip: codec; rsk_demux.hip: receive demux; rsk_deliver.hip: payload delivery;
+// rsk_control.hip: control packets and the keepalive timer).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,10 +20,18 @@ struct ShimIO;  // rsk_kernels.hip
 
 namespace rsk {
 // Device scratch of one kind for the calls ordered on one stream.
-enum WsKind { WS_COMPACT = 0, WS_SEQ = 1, WS_DEMUX = 2, WS_ENC = 3, WS_DELIVER = 4, WS_KINDS = 5 };
+enum WsKind { WS_COMPACT = 0, WS_SEQ = 1, WS_DEMUX = 2, WS_ENC = 3, WS_DELIVER = 4, WS_CONTROL = 5, WS_KINDS = 6 };
 // WS_DELIVER (rsk_deliver.hip): one 64-bit sum per tile of kDeliverTile positions, and the total
 constexpr uint32_t kDeliverTile = 1024;
 inline size_t deliver_ws_bytes(uint32_t n) { return ((size_t)(n + kDeliverTile - 1u) / kDeliverTile + 1u) * 8u; }
+// WS_CONTROL (rsk_control.hip): two 32-bit counts per tile of kControlTile packets (rsk_control_batch) or
+// kFlushTile rows (rsk_keepalive_flush), and the totals; never less than the largest table's flush needs,
+// so a reserve for any batch size covers the flush
+constexpr uint32_t kControlTile = 2048, kFlushTile = 1024;
+inline size_t control_ws_bytes(uint32_t n) {
+    const size_t tiles = ((size_t)n + kControlTile - 1u) / kControlTile, rows = RSK_CONN_MAX_ROWS / kFlushTile;
+    return ((tiles > rows ? tiles : rows) + 1u) * 8u;
+}
 struct WsBuf {
     void *p = nullptr;
     size_t bytes = 0;

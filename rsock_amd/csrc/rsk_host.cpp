@@ -2,7 +2,8 @@
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
 // (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
-// (rsk_conn_*_host); the single-frame slot staging, the capture filter's text form and the connection
+// (rsk_conn_*_host) with its control packets and keepalive timer (rsk_control_host,
+// rsk_keepalive_flush_host); the single-frame slot staging, the capture filter's text form and the connection
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
@@ -289,6 +290,158 @@ extern "C" int rsk_conn_expand_host(const rsk_conn_table *t, uint32_t n, const u
         bt->fetch_add(nb, std::memory_order_relaxed);
     });
     if (out->n_bad) *out->n_bad = bad_total.load();
+    return RSK_OK;
+}
+
+// ---- control packets and the keepalive timer (rsk_control_batch / rsk_keepalive_flush): the host twins ----
+namespace {
+
+bool ctl_msgs_any(const rsk_ctl_msgs &m) {
+    return m.cmd || m.body || m.id || m.src || m.avoid_key || m.pay_off || m.pay_len;
+}
+
+void ctl_put_msg(const rsk_ctl_msgs &m, uint32_t k, uint8_t cmd, uint64_t body, const uint8_t *id, uint32_t src,
+                 uint64_t avoid) {
+    if (m.cmd) m.cmd[k] = cmd;
+    if (m.body) m.body[k] = body;
+    if (m.id) {
+        if (id) std::memcpy(m.id + 8ull * k, id, 8);
+        else std::memset(m.id + 8ull * k, 0, 8);
+    }
+    if (m.src) m.src[k] = src;
+    if (m.avoid_key) m.avoid_key[k] = avoid;
+    if (m.pay_off) m.pay_off[k] = 8ull * k;
+    if (m.pay_len) m.pay_len[k] = 8;
+}
+
+}  // namespace
+
+// Classification, body read and lookup per packet over shards; then one walk in packet order for the
+// per-row effects, the counts and the message list.
+extern "C" int rsk_control_host(const rsk_conn_table *t, uint32_t n, const rsk_control_in *in, const rsk_control_out *out,
+                                int nthreads) {
+    if (!in || !out || !conn_tab_lookup_ok(t)) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    if (n && (!in->status || !in->cmd || !in->arena || !in->base_off || !in->pay_off || !in->pay_len || (by_id && !in->id)))
+        return RSK_EINVAL;
+    if ((in->tcp_sp == nullptr) != (in->tcp_dp == nullptr)) return RSK_EINVAL;
+    if (in->miss && !in->conn_key) return RSK_EINVAL;
+    const bool list = ctl_msgs_any(out->msgs);
+    if (list && !out->msgs.n_msg) return RSK_EINVAL;
+    if (n > RSK_MAX_BATCH) return RSK_EINVAL;
+    if (out->rst_first) std::memset(out->rst_first, 0xFF, 4ull * t->capacity);
+    std::vector<uint8_t> kind(n);
+    std::vector<uint64_t> arg(n);
+    std::vector<uint32_t> conn(n);
+    uint8_t *kd = kind.data();
+    uint64_t *ag = arg.data();
+    uint32_t *cn = conn.data();
+    const rsk_control_in a = *in;
+    const HostConnTab h{t};
+    const uint32_t cap = t->capacity;
+    const bool close_ok = in->tcp_sp && !by_id;
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        for (uint32_t i = lo; i < hi; ++i) {
+            uint8_t k = RSK_CTL_NONE;
+            uint64_t v = 0;
+            uint32_t row = RSK_CONN_NONE;
+            if (a.status[i] == RSK_RECV_VALID) {
+                const uint8_t cm = a.cmd[i];
+                if (cm > 4u) {
+                    k = RSK_CTL_UNKNOWN;
+                } else if (cm != RSK_CMD_DATA) {
+                    const uint32_t need = cm == RSK_CMD_CONV_RST ? 4u : 8u;
+                    if (a.pay_len[i] < need) {
+                        k = RSK_CTL_SHORT;
+                    } else {
+                        k = cm;  // RSK_CTL_CONV_RST .. RSK_CTL_KA_RESP are the cmd values
+                        const uint8_t *p = a.arena + a.base_off[i] + (a.inner_off ? a.inner_off[i] : 0u) + a.pay_off[i];
+                        if (need == 4u) {
+                            uint32_t w;
+                            std::memcpy(&w, p, 4);  // decode_uint32 (ConnReset.cpp:50)
+                            v = w;
+                        } else {
+                            v = load64(p);  // KeyGenerator::DecodeKeySafe
+                        }
+                    }
+                }
+            } else if (a.status[i] == RSK_RECV_CLOSE && close_ok) {
+                k = RSK_CTL_TCP_CLOSE;
+                v = rsk_key_for_tcp(a.tcp_sp[i], a.tcp_dp[i]);
+            }
+            if (k >= RSK_CTL_NETCONN_RST && k <= RSK_CTL_TCP_CLOSE)
+                row = rsk::conn_lookup(h, cap, by_id, v, by_id ? load64(a.id + 8ull * i) : 0ull);
+            kd[i] = k;
+            ag[i] = v;
+            cn[i] = row;
+        }
+    });
+    uint32_t n_msg = 0, n_ctl = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint8_t k = kind[i];
+        const uint32_t row = conn[i];
+        n_ctl += k != RSK_CTL_NONE;
+        if (out->kind) out->kind[i] = k;
+        if (out->arg) out->arg[i] = arg[i];
+        if (out->conn) out->conn[i] = row;
+        if (row != RSK_CONN_NONE) {
+            if (out->rst_first && (k == RSK_CTL_NETCONN_RST || k == RSK_CTL_TCP_CLOSE) && out->rst_first[row] == 0xFFFFFFFFu)
+                out->rst_first[row] = i;
+            if (out->ka_tries && k == RSK_CTL_KA_RESP) out->ka_tries[row] = RSK_KA_NONE;
+        }
+        const uint8_t *idp = in->id ? in->id + 8ull * i : nullptr;
+        if (k == RSK_CTL_KA_REQ) {
+            const bool hit = row != RSK_CONN_NONE;
+            if (list) ctl_put_msg(out->msgs, n_msg, hit ? RSK_CMD_KEEP_ALIVE_RESP : RSK_CMD_NETCONN_RST, arg[i], idp, i,
+                                  hit ? 0ull : arg[i]);
+            ++n_msg;
+        } else if (in->miss && in->miss[i] == RSK_RECV_VALID) {
+            if (list) ctl_put_msg(out->msgs, n_msg, RSK_CMD_NETCONN_RST, in->conn_key[i], idp, i, in->conn_key[i]);
+            ++n_msg;
+        }
+    }
+    if (out->msgs.n_msg) *out->msgs.n_msg = n_msg;
+    if (out->n_ctl) *out->n_ctl = n_ctl;
+    return RSK_OK;
+}
+
+// Rows in order on the caller's thread (the lists are in row order; nthreads is taken for symmetry).
+extern "C" int rsk_keepalive_flush_host(const rsk_conn_table *t, const rsk_keepalive *ka, const rsk_keepalive_out *out,
+                                        int /*nthreads*/) {
+    if (!ka || !out || !conn_tab_ok(t) || !t->state || !t->conn_key) return RSK_EINVAL;
+    if (!ka->ka_tries || !ka->established_ms) return RSK_EINVAL;
+    if (ka->max_retry < 1u || ka->max_retry > 254u) return RSK_EINVAL;
+    const bool list = ctl_msgs_any(out->msgs);
+    if ((list && !out->msgs.n_msg) || (out->dead_rows && !out->n_dead)) return RSK_EINVAL;
+    uint32_t n_msg = 0, n_dead = 0;
+    const int32_t delay = (int32_t)ka->request_delay_ms;
+    for (uint32_t r = 0; r < t->capacity; ++r) {
+        const uint8_t st = t->state[r];
+        if (!(st & RSK_CONN_LIVE)) {  // removeInvalidRequest
+            ka->ka_tries[r] = RSK_KA_NONE;
+            continue;
+        }
+        if (!ka->online) continue;
+        uint32_t tries = ka->ka_tries[r];
+        const uint64_t est = ka->established_ms[r];
+        // canSendRequest: `int df = timestampMs - conn->EstablishedTimeStampMs()`, truncation included
+        if (!(st & RSK_CONN_NEW) && ka->now_ms > est && (int32_t)(uint32_t)(ka->now_ms - est) >= delay) {
+            const bool had = tries != RSK_KA_NONE;
+            tries = had ? (tries + 1u) & 0xFFu : 0u;
+            if (!had || tries < ka->max_retry) {
+                if (list) ctl_put_msg(out->msgs, n_msg, RSK_CMD_KEEP_ALIVE_REQ, t->conn_key[r], t->id ? t->id + 8ull * r : nullptr, r, 0ull);
+                ++n_msg;
+            }
+        }
+        if (tries != RSK_KA_NONE && tries >= ka->max_retry) {  // keep alive timeout
+            tries = RSK_KA_NONE;
+            if (out->dead_rows) out->dead_rows[n_dead] = r;
+            ++n_dead;
+        }
+        ka->ka_tries[r] = (uint8_t)tries;
+    }
+    if (out->msgs.n_msg) *out->msgs.n_msg = n_msg;
+    if (out->n_dead) *out->n_dead = n_dead;
     return RSK_OK;
 }
 

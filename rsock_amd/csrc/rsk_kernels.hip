@@ -3215,6 +3215,11 @@ int rsk_reserve_stream(rsk_ctx *c, uint32_t n_max, void *stream) {
         void *dl = nullptr;
         r = rsk::stream_ws(c, (hipStream_t)stream, rsk::WS_DELIVER, rsk::deliver_ws_bytes(n_max), &dl);
     }
+    // the tile counts of rsk_control_batch / rsk_keepalive_flush (rsk_control.hip: 8 B per 2048 packets)
+    if (!r) {
+        void *ct = nullptr;
+        r = rsk::stream_ws(c, (hipStream_t)stream, rsk::WS_CONTROL, rsk::control_ws_bytes(n_max), &ct);
+    }
     // the two-pass encode's header records (32 B per packet), for a context that encodes: held to the
     // two-pass path, or AUTO with an encode call behind it (a decode- or demux-only context
     // does not pay 32 B per packet for them).  A capture cannot allocate them: without this reserve

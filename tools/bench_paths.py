@@ -5,7 +5,9 @@ decode (verify + compaction), parse_decode (pcap parse of the Ethernet wire pack
 deliver / deliver_demux / deliver_plan (the VALID payloads packed in valid_idx / demux order; offsets only),
 verify_wire_eth / verify_wire_raw4 (IPv4 + TCP checksum check of the wire packets built above),
 conn_resolve / conn_resolve_64conn / conn_resolve_miss / conn_expand (the connection table: the decoded
-batch against its own connKeys, 64 connections, half of the keys absent; the send side's gather).
+batch against its own connKeys, 64 connections, half of the keys absent; the send side's gather) /
+control_<config> / control_dense / keepalive_flush_28k / keepalive_flush_1m (control packets and the
+keepalive timer on the connection table; the _kind rows write kind and the messages only).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -26,7 +28,7 @@ def main():
     ap.add_argument("--wire-align", type=int, default=0,
                     help="wire packet pitch alignment (bytes); 0 = the frame slot rule (128 with PAD128 for "
                          "mixed lengths, else 16)")
-    ap.add_argument("--only", default="", help="time only these paths (comma list), e.g. demux,demux_64conn")
+    ap.add_argument("--only", default="", help="time only these paths (comma list; a trailing * matches a prefix), e.g. demux,demux_64conn")
     ap.add_argument("--copy-yardstick", action="store_true",
                     help="also time tools/libhbm_probe.so's dense 16-B copy of the delivered byte count (rows "
                          "dense_copy@GRID) and report deliver's time over the fastest of them")
@@ -295,10 +297,93 @@ def main():
             for grid in (2048, 8192, 65536):
                 ops[f"dense_read_{name}@{grid}"] = lambda grid=grid, per=per: hp.probe_run(
                     1, wiree.data_ptr(), ysink.data_ptr(), n * per, grid, s.cuda_stream)
+    # control packets and the keepalive timer (rsk_control_batch / rsk_keepalive_flush): the decoded batch
+    # with its own cmd column against the table of its connKeys (control_<config>: C4 has 5 % control
+    # packets, C3 none -- the cost of finding nothing), the same batch with 20 % control packets
+    # (control_dense), and the timer over 28 K and 2^20 rows.  The bodies are written into a copy of the
+    # frames (~80 % keys of the table), so the frames the other rows decode stay as they are; a config whose
+    # frames exceed 2 GiB is not copied and gets no control_dense row (its own batch has no body to write).
+    ctl_rows = {}
+    c_own = ((ddec.status == 1) & (ddec.cmd >= 1) & (ddec.cmd <= 4)).nonzero().flatten()
+    dense_cmd = torch.where(torch.rand(n, device=dev, generator=gk) < 0.2,
+                            torch.randint(1, 5, (n,), device=dev, generator=gk, dtype=torch.int64).to(torch.uint8), ddec.cmd)
+    dense_cmd = torch.where(ddec.status == 1, dense_cmd, ddec.cmd)
+    c_dense = ((ddec.status == 1) & (dense_cmd >= 1) & (dense_cmd <= 4)).nonzero().flatten()
+    want_dense = w.frame.numel() <= (1 << 31)
+    cframe = w.frame.clone() if (want_dense or c_own.numel()) and w.frame.numel() <= (1 << 31) else w.frame
+    c_len = ddec.pay_len.clone()
+    if cframe is not w.frame:
+        idx = c_dense if want_dense else c_own
+        k_body = own_keys[torch.randint(0, own_keys.numel(), (idx.numel(),), device=dev, generator=gk)]
+        k_body = torch.where(torch.rand(idx.numel(), device=dev, generator=gk) < 0.8, k_body, k_body ^ (1 << 40))
+        at = w.frame_off[idx] + ddec.pay_off[idx].to(torch.int64)
+        cframe[(at[:, None] + torch.arange(8, device=dev)[None, :]).flatten()] = k_body.view(torch.uint8)
+        c_len[idx] = torch.clamp(c_len[idx], min=8)
+    ctl_full = rc.ControlBuffers.alloc(n, dev, capacity=tab_own.capacity)
+    ctl_kind = rc.ControlBuffers.alloc(n, dev, capacity=tab_own.capacity)
+    ctl_kind.arg = ctl_kind.conn = None
+    ctl_tries = torch.zeros(tab_own.capacity, dtype=torch.uint8, device=dev)
+
+    def control_op(cmd_col, out):
+        return lambda: cx.control_batch(tab_own, ddec.status, cmd_col, ddec.pay_off, c_len, cframe, w.frame_off, out,
+                                        id=ddec.id, ka_tries=ctl_tries, stream=s)
+
+    ops[f"control_{args.config}"] = control_op(ddec.cmd, ctl_full)
+    ops[f"control_{args.config}_kind"] = control_op(ddec.cmd, ctl_kind)
+    if want_dense:
+        ops["control_dense"] = control_op(dense_cmd, ctl_full)
+        ops["control_dense_kind"] = control_op(dense_cmd, ctl_kind)
+    for k in [k for k in ops if k.startswith("control_")]:
+        ops[k]()
+        torch.cuda.synchronize()
+        kinds = torch.bincount(ctl_full.kind.to(torch.int64), minlength=8).tolist() if not k.endswith("_kind") else None
+        ctl_rows[k] = {"n_ctl": int(ctl_full.n_ctl.item() if kinds else ctl_kind.n_ctl.item()),
+                       "n_msg": int(ctl_full.n_msg.item() if kinds else ctl_kind.n_msg.item())}
+        if kinds:
+            look = (ctl_full.kind >= 2) & (ctl_full.kind <= 4)
+            ctl_rows[k].update(kinds=kinds, lookups=int(look.sum().item()),
+                               hits=int((look & (ctl_full.conn != -1)).sum().item()))
+    own_ctl = ctl_rows[f"control_{args.config}"]
+    assert own_ctl["n_ctl"] == int(((ddec.status == 1) & (ddec.cmd != 0)).sum().item())
+    # the timer: every row LIVE and old enough, a third of them with a pending request
+    ka = {}
+    for label, cap in (("28k", 28232), ("1m", 1 << 20)):
+        t = rc.ConnTable.alloc(cap, dev)
+        t.state.fill_(A.CONN_LIVE | A.CONN_ALIVE)
+        t.conn_key.copy_(torch.arange(cap, device=dev, dtype=torch.int64) + (1 << 28))
+        tries0 = torch.where(torch.arange(cap, device=dev) % 3 == 0, 1, 255).to(torch.uint8)
+        tries, est = tries0.clone(), torch.zeros(cap, dtype=torch.int64, device=dev)
+        fo = rc.ControlBuffers.alloc(0, dev, capacity=cap, m=cap)
+        ka[label] = (t, tries, tries0, est, fo)
+        # every call starts from the same tries (the 1-B column copied back on the stream is part of the row)
+        ops[f"keepalive_flush_{label}"] = lambda a=ka[label]: (a[1].copy_(a[2]), cx.keepalive_flush(
+            a[0], a[1], a[3], 10**9, a[4], stream=s))
+        ops[f"keepalive_flush_{label}"]()
+        torch.cuda.synchronize()
+        assert int(fo.n_msg.item()) == cap and int(fo.n_dead.item()) == 0
+        ctl_rows[f"keepalive_flush_{label}"] = {"rows": cap, "n_msg": cap, "n_dead": 0}
+    # algorithmic bytes per packet: status and cmd read, the per-packet outputs written, and per control
+    # packet pay_len 2 + base_off 8 + pay_off 2 + id 8 + body 8 read; per message 37 written
+    def ctl_alg(k):
+        r = ctl_rows[k]
+        per_out = 1 if k.endswith("_kind") else 1 + 8 + 4
+        return 2 + per_out + ((r["n_ctl"] * 28 + r["n_msg"] * 37) / n)
+
+    ka_alg = 1 + 1 + 8 + 1 + 8 + 37  # state, tries, est read; tries written; conn_key read; the message written
+    if args.read_yardstick:
+        for k in [k for k in ops if k.startswith("control_")]:
+            for grid in (2048, 8192):
+                ops[f"dense_read_{k}@{grid}"] = lambda grid=grid, b=int(n * ctl_alg(k)): hp.probe_run(
+                    1, wiree.data_ptr(), ysink.data_ptr(), b, grid, s.cuda_stream)
+        for label, cap in (("28k", 28232), ("1m", 1 << 20)):
+            for grid in (256, 2048):
+                ops[f"dense_read_keepalive_flush_{label}@{grid}"] = lambda grid=grid, b=cap * ka_alg: hp.probe_run(
+                    1, wiree.data_ptr(), ysink.data_ptr(), b, grid, s.cuda_stream)
     nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
-        ops = {k: f for k, f in ops.items() if k in keep}
+        # an entry ending in * keeps every path it is a prefix of
+        ops = {k: f for k, f in ops.items() if k in keep or any(e.endswith("*") and k.startswith(e[:-1]) for e in keep)}
     times = {k: [] for k in ops}
     for _ in range(args.rounds):
         for k, f in ops.items():
@@ -348,6 +433,13 @@ def main():
     alg["conn_expand"] = conn_alg["conn_expand"]
     alg.update({k: conn_alg["conn_resolve"] for k in ops if k.startswith("dense_read_resolve@")})
     alg.update({k: conn_alg["conn_expand"] for k in ops if k.startswith("dense_read_expand@")})
+    items = {}  # rows that do not run over the batch's n packets: the timer's rows
+    for k in ops:
+        base = k[len("dense_read_"):].split("@")[0] if k.startswith("dense_read_") else k
+        if base.startswith("control_"):
+            alg[k] = ctl_alg(base)
+        elif base.startswith("keepalive_flush_"):
+            alg[k], items[k] = ka_alg, ctl_rows[base]["rows"]
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -356,7 +448,8 @@ def main():
     for k, t in times.items():
         m = float(np.median(t))
         a = alg.get(k, alg["encode_wire_eth" if "_eth_" in k else "encode_wire_raw4"])
-        out[k] = {"ms": round(m, 4), "Mpkt_s": round(n / m / 1e3, 1), "GBps_alg": round(n * a / m / 1e6, 1)}
+        cnt = items.get(k, n)
+        out[k] = {"ms": round(m, 4), "Mpkt_s": round(cnt / m / 1e3, 1), "GBps_alg": round(cnt * a / m / 1e6, 1)}
     res = {"config": args.config, "packets": n, "wire_pitch": [p4, pe], "demux_segments": nseg,
            "deliver_bytes": dl_bytes, "paths": out}
     dense = [v["ms"] for k, v in out.items() if k.startswith("dense_copy@")]
@@ -381,6 +474,15 @@ def main():
             for k in rows:
                 if k in out:
                     res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dr), 3)
+    ctl = [k for k in out if k.startswith(("control_", "keepalive_flush_"))]
+    if ctl:
+        res["control_rows"] = {k: dict(ctl_rows[k], bytes_alg=round(alg[k], 2)) for k in ctl}
+    for k in ctl:
+        dr = [v["ms"] for q, v in out.items() if q.startswith(f"dense_read_{k}@")]
+        if dr:
+            res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dr), 3)
+        if k.startswith("control_") and "conn_resolve" in out:
+            res[f"{k}_over_conn_resolve"] = round(out[k]["ms"] / out["conn_resolve"]["ms"], 3)
     print(json.dumps(res))
 
 
