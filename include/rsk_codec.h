@@ -488,7 +488,12 @@ typedef struct rsk_demux_out {
     uint32_t *n_seg;     /* [1]                                                                   */
     uint32_t *n_valid;   /* [1]                                                                   */
 } rsk_demux_out;
-/* n <= 2^30.  Workspace (per stream, grown on demand): about 75 B per packet.  GROUP_BARRIER runs
+/* n <= 2^30.  Workspace (per stream, grown on demand): about 75 B per packet.  Its key table is kept
+ * all-ones between calls at a place that depends on the table size alone, so calls of any batch
+ * sizes may follow each other on a stream.  A call captured into a hipGraph needs the stream's
+ * workspace to exist at the largest size that will run on that stream (rsk_reserve_stream does not
+ * size it: run one eager call of that size first); growing it later frees what the graph points at.
+ * GROUP_BARRIER runs
  * two group-bys (the control packets by IdBuf, then every packet by the key with each DATA packet's
  * epoch inside its IdBuf), writing
  * the first one's result to `out` before the second overwrites it. */

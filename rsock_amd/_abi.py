@@ -319,6 +319,19 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     return lib
 
 
+def demux_ws_layout(lib: ctypes.CDLL, n: int) -> tuple[int, int, int]:
+    """rsk__demux_ws_layout (internal, host only, not in the header): (key table offset, key table
+    bytes, total bytes) of the demux scratch for a batch of n packets."""
+    fn = lib.rsk__demux_ws_layout
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
+    out = (ctypes.c_uint64 * 3)()
+    rc = fn(n, out)
+    if rc != 0:
+        raise ValueError(f"rsk__demux_ws_layout({n}) failed: rc={rc}")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def header_symbols(header_paths: list[str] | None = None) -> list[str]:
     """Names of every function declared in include/rsk_codec.h and include/rsk_rconn.h."""
     import re

@@ -889,6 +889,7 @@ struct DmWs {
     unsigned long long *slots;  // the key table, then the look-back states (k_dm_fill)
     unsigned long long *st_v, *st_c, *st_l, *st_r;
     size_t state_bytes;
+    size_t slots_off;  // the key table's offset in the scratch: a function of tsize alone (dm_layout)
     uint32_t *tflag;  // == tsize: the table is all-ones for this size (k_dm_final), else the fill writes it
     uint32_t *nv, *nseg;
     uint32_t nb, nt, tsize;
@@ -909,7 +910,20 @@ size_t dm_layout(uint32_t n, uint8_t *base, DmWs *w) {
         return p;
     };
     DmWs d;
-    d.tflag = (uint32_t *)take(8);  // first, at a fixed place for every batch size
+    // The flag word, then the key table: both at offsets that depend on T alone.  The flag speaks of
+    // the table's bytes, so every batch size with this table size must find the table at the same
+    // place: behind the per-packet arrays its offset moved with n, and a smaller batch of the same T
+    // took an earlier call's sort buffers for a clean table (RSK_DEVERR_TABLE).  The look-back states
+    // follow the table (one memset covers both, demux_pass), then everything sized by n.
+    d.tflag = (uint32_t *)take(8);
+    d.slots_off = off;
+    d.slots = (unsigned long long *)take(8ull * T);
+    const size_t st0 = off;
+    d.st_v = (unsigned long long *)take(8ull * nt);
+    d.st_c = (unsigned long long *)take(8ull * nt);
+    d.st_l = (unsigned long long *)take(8ull * nt);
+    d.st_r = (unsigned long long *)take(8ull * 4 * 256 * nt);
+    d.state_bytes = off - st0;
     d.cidx = (uint32_t *)take(4ull * n);
     d.hslot = (uint32_t *)take(4ull * n);
     d.rank_at = (uint32_t *)take(4ull * n);
@@ -923,13 +937,6 @@ size_t dm_layout(uint32_t n, uint8_t *base, DmWs *w) {
     d.ghist = (uint32_t *)take(4ull * 4 * 256);
     d.nv = (uint32_t *)take(8);
     d.nseg = (uint32_t *)take(8);
-    d.slots = (unsigned long long *)take(8ull * T);
-    const size_t st0 = off;
-    d.st_v = (unsigned long long *)take(8ull * nt);
-    d.st_c = (unsigned long long *)take(8ull * nt);
-    d.st_l = (unsigned long long *)take(8ull * nt);
-    d.st_r = (unsigned long long *)take(8ull * 4 * 256 * nt);
-    d.state_bytes = off - st0;
     d.nb = nb;
     d.nt = nt;
     d.tsize = T;
@@ -1003,8 +1010,13 @@ int demux_pass(rsk_ctx *c, const DmIn &a, const DmWs &w, const rsk_demux_out *ou
     // likely dirty -> one memset of table and states (a blit, faster than the kernel: C4 0.080 vs
     // 0.085 ms); likely clean -> k_dm_fill, which checks the device flag itself (a stale hint is only
     // slower, never wrong)
+    // A call that is being captured always records k_dm_fill: the hint read now says nothing about the
+    // replays, and the kernel reads the flag word at each of them.  (It also keeps the 8 T + states
+    // bytes out of a memset node: a graph recorded with that memset ended its first replay in an
+    // illegal memory access, where the same graph with k_dm_fill in its place replays correctly.)
     uint32_t *hint = c->enc_stat_dev ? c->enc_stat_dev + 1 : nullptr;
-    const bool likely_clean = c->enc_stat_host && __atomic_load_n(c->enc_stat_host + 1, __ATOMIC_RELAXED) == w.tsize;
+    const bool likely_clean = rsk::capturing(s) ||
+                              (c->enc_stat_host && __atomic_load_n(c->enc_stat_host + 1, __ATOMIC_RELAXED) == w.tsize);
     if (!likely_clean) {
         hipError_t e = hipMemsetAsync(w.slots, 0xff, (size_t)w.tsize * 8u + w.state_bytes, s);
         if (e != hipSuccess) { rsk::set_error("hipMemsetAsync(table)", e); return RSK_EDEVICE; }
@@ -1099,6 +1111,17 @@ extern "C" int rsk_demux_batch(rsk_ctx *c, uint32_t n, const rsk_demux_in *in, u
     if ((r = rsk::launch_check("k_dm_gep"))) return r;
     a.xep = w.pep;
     return demux_pass(c, a, w, out, s);
+}
+
+// internal, host only (not in the public header; tests): where dm_layout puts the key table for a batch
+// of n packets -- out = {table offset, table bytes, total bytes} of the WS_DEMUX scratch
+extern "C" int rsk__demux_ws_layout(uint32_t n, uint64_t out[3]) {
+    if (!out || n == 0 || n > (1u << 30)) return RSK_EINVAL;
+    DmWs w;
+    out[2] = dm_layout(n, nullptr, &w);
+    out[0] = w.slots_off;
+    out[1] = 8ull * w.tsize;
+    return RSK_OK;
 }
 
 // =============================================================================================

@@ -82,6 +82,36 @@ def test_host_key_helpers_match_reference_fixtures():
         assert lib.rsk_key_for_udp(int(a), int(b)) == int(ku)
 
 
+def _table_size(n: int) -> int:
+    """rsk_demux.hip table_size: the power of two >= 2 n, at least 64."""
+    t = 64
+    while t < 2 * n:
+        t <<= 1
+    return t
+
+
+def test_demux_table_offset_depends_on_table_size_alone():
+    """The demux scratch's "table is clean" word names the table size only (k_dm_final, k_dm_fill), so
+    the key table must lie at the same offset for every batch size with that table size: otherwise a
+    smaller batch finds its table over an earlier call's per-packet arrays and skips the fill.  Checked
+    on the host through rsk__demux_ws_layout (dm_layout's own numbers), for n = 1 .. 70000 in steps,
+    every power of two +-1 up to 2^20 and the sizes the GPU call-sequence tests use."""
+    lib = _abi.load()
+    ns = set(range(1, 70001, 37)) | set(range(1, 300)) | {1025, 1300, 1700, 2048, 4097, 4800, 6000, 8192, 70000}
+    for k in range(21):
+        ns |= {max(1, (1 << k) - 1), 1 << k, (1 << k) + 1}
+    by_t = {}
+    for n in sorted(ns):
+        off, nbytes, total = _abi.demux_ws_layout(lib, n)
+        t = _table_size(n)
+        assert nbytes == 8 * t, n
+        assert off % 16 == 0, (n, off)  # the fill stores 16 B at a time
+        assert off + nbytes <= total, (n, off, nbytes, total)
+        first = by_t.setdefault(t, (n, off))
+        assert off == first[1], f"table of {t} slots at {off} for n = {n}, at {first[1]} for n = {first[0]}"
+    assert len(by_t) >= 15
+
+
 def test_constants_match_header():
     text = open(os.path.join(ROOT, "include", "rsk_codec.h")).read()
     import re
