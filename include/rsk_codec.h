@@ -49,6 +49,16 @@
  *                            (conn/IAppGroup.cpp:103-116)
  *   rsk_keepalive_flush   <- NetConnKeepAlive::OnFlush / canSendRequest (callbacks/NetConnKeepAlive.cpp:110-145,
  *                            :168-178)
+ *   rsk_conv_resolve_batch <- SubGroup::OnRecv's lookup of BuildConvKey(dst, conv) in the packet's SubGroup
+ *                            (server/SubGroup.cpp:31-50, server/ServerGroup.cpp:44-60), ClientGroup::OnRecv's
+ *                            lookup of conv in mConvMap and its SendConvRst (client/ClientGroup.cpp:65-80,
+ *                            callbacks/ConnReset.cpp:34-41), ConnReset::OnRecvConvRst (:67-77) and the
+ *                            curr_in++ of IConn::DataStat (conn/IConn.cpp:63-79)
+ *   rsk_conv_send_batch   <- SubGroup::sconnSend / ClientGroup::cconSend setting the head's conv, and
+ *                            IConn::Send -> afterSend's curr_out++ (conn/IConn.cpp:63-79)
+ *   rsk_conv_flush        <- IGroup::Flush (conn/IGroup.cpp:81-107) with IConn::DataStat::Flush
+ *   rsk_conv_table        <- a group's mConns at the app level (a server's SubGroups, a ClientGroup's
+ *                            mConvMap) and the DataStat of every conv in it
  */
 #ifndef RSK_CODEC_H
 #define RSK_CODEC_H
@@ -827,7 +837,7 @@ typedef struct rsk_ctl_msgs {  /* every array optional; n_msg required when any 
     uint32_t *src;        /* [m] packet index (rsk_control_batch) or row (rsk_keepalive_flush) */
     uint64_t *avoid_key;  /* [m] */
     uint64_t *pay_off;    /* [m] 8k */
-    uint16_t *pay_len;    /* [m] 8 */
+    uint16_t *pay_len;    /* [m] 8 (4 from rsk_conv_resolve_batch) */
     uint32_t *n_msg;      /* [1] */
 } rsk_ctl_msgs;
 typedef struct rsk_control_out {  /* every output optional */
@@ -884,6 +894,160 @@ int rsk_control_host(const rsk_conn_table *tab, uint32_t n, const rsk_control_in
                      int nthreads);
 int rsk_keepalive_flush_host(const rsk_conn_table *tab, const rsk_keepalive *ka, const rsk_keepalive_out *out,
                              int nthreads);
+
+/* ---- conv table: a DATA packet's conv, the convs' activity counts and their flush ------------------ */
+/* The reference's last lookup before a payload reaches anybody: on a server SubGroup::OnRecv looks
+ * BuildConvKey(info->dst, head->Conv()) up in the SubGroup of the packet's IdBuf (server/SubGroup.cpp:31-50,
+ * server/ServerGroup.cpp:44-60); on a client ClientGroup::OnRecv looks head->Conv() up in mConvMap
+ * (client/ClientGroup.cpp:65-80) and answers an unknown conv with SendConvRst (callbacks/ConnReset.cpp:34-41).
+ * Each conv counts its packets (IConn::DataStat, conn/IConn.cpp:63-79: curr_in++ / curr_out++), and
+ * IGroup::Flush (conn/IGroup.cpp:81-107) closes the convs that went quiet.  Here that level is a second
+ * table of `capacity` rows in caller-owned device columns, with the rules of the connection table above:
+ * the host edits rows with ordinary copies and calls rsk_conv_index_build after any change to state,
+ * conv, dst or id; the counter columns need no rebuild.
+ *   receive  ... -> rsk_conn_resolve_batch (hit) -> rsk_control_batch (kind, arg) -> rsk_conv_resolve_batch
+ *            -> conv_row[i]; rsk_demux_batch / rsk_deliver_batch hand the bytes to the rows
+ *   send     rsk_conv_send_batch(conv_row) -> conv, dst, id (rsk_encode_in) -> ... encode ... ->
+ *            rsk_conv_send_batch(conv_row, sent = the encode's status) counts what was sent
+ *   timer    rsk_conv_flush -> the rows to close
+ * The key of a row is the 64-bit word ((uint64_t)dst << 32) | conv with RSK_CONV_BY_DST, else conv; with
+ * RSK_CONV_BY_ID it is paired with the row's IdBuf word (injective, as the reference's "conv:ip:conv"
+ * string inside one SubGroup is).  A client is flags 0, a server both; any combination is valid.  The
+ * index has the layout, hash and probe rule of the connection table's: rsk_conn_index_bytes(capacity, 0)
+ * sizes it, one built on the host is valid on the device and the reverse, the lowest LIVE row of a key
+ * wins. */
+#define RSK_CONV_BY_DST 0x1u /* the key includes the TcpInfo dst: a server's SubGroup               */
+#define RSK_CONV_BY_ID  0x2u /* one key space per IdBuf: a server's SubGroups                        */
+
+typedef struct rsk_conv_table {  /* device pointers, caller-owned, `capacity` rows */
+    uint32_t capacity, flags;    /* capacity in [1, RSK_CONN_MAX_ROWS]; RSK_CONV_BY_DST | RSK_CONV_BY_ID */
+    const uint8_t  *state;       /* [C] RSK_CONN_LIVE = the row is in mConns */
+    const uint32_t *conv;        /* [C] */
+    const uint32_t *dst;         /* [C] BY_DST only (also what rsk_conv_send_batch hands out) */
+    const uint8_t  *id;          /* [C*8], 8-B aligned; BY_ID only (also for rsk_conv_send_batch) */
+    uint32_t *cur_in, *cur_out;  /* [C] DataStat::curr_in / curr_out; wrap mod 2^32 as the reference's uint32_t */
+    uint32_t *prev_in, *prev_out;/* [C] DataStat::prev_in / prev_out */
+    uint8_t  *alive;             /* [C] DataStat::mAlive; the host sets 1 when it creates a row */
+    uint32_t *index;             /* opaque, rsk_conn_index_bytes(capacity, 0) bytes, 16-B aligned */
+} rsk_conv_table;
+
+/* As rsk_conn_index_build: two launches of the same kernel (clear, insert the LIVE rows), no scratch, no
+ * incremental insert; *n_dup (device, optional, written) = the LIVE rows that lost their key to a lower
+ * row.  RSK_EINVAL: a NULL ctx, tab, state, conv or index; dst / id missing with their flag; unknown
+ * flags; a capacity outside [1, RSK_CONN_MAX_ROWS]; an index that is not 16-B aligned; an id column
+ * that is not 8-B aligned. */
+int rsk_conv_index_build(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t *n_dup, void *stream);
+
+/* Receive.  Per packet i:
+ *   DATA      examined iff status[i] == RSK_RECV_VALID && cmd[i] == RSK_CMD_DATA && (hit == NULL || hit[i])
+ *             (a client packet of an unknown connKey never reaches ClientGroup::OnRecv: INetGroup::Input
+ *             returns ERR_NO_CONN first).  conv_row[i] = the LIVE row of (id[i], dst[i], conv[i]) -- each
+ *             part only with its flag -- or RSK_CONN_NONE.  With tab->cur_in given, every examined packet
+ *             that found row r adds 1 to cur_in[r] (IConn::Input -> afterInput(n > 0); a VALID packet has
+ *             pay_len >= 1).  The sums are exact whatever the skew -- all of a batch on one row, or every
+ *             packet on another row -- and equal rows are combined on chip: no global atomic per packet.
+ *   CONV_RST  with ctl_kind / ctl_arg given (rsk_control_batch's kind / arg; both or neither), a packet
+ *             that is not examined and whose kind is RSK_CTL_CONV_RST is looked up as (id[i], dst[i],
+ *             (uint32_t)ctl_arg[i]) on a table with RSK_CONV_BY_DST: conv_row[i] = the row or NONE, and
+ *             rst_first[r] (optional, [capacity]; filled with 0xFFFFFFFF on the stream, then atomicMin) =
+ *             the smallest such packet index that hit r: OnRecvConvRst -> CloseConn.  It adds nothing to
+ *             cur_in.  On a table WITHOUT RSK_CONV_BY_DST (a client) a CONV_RST never hits: conv_row
+ *             NONE, no rst_first.  Reproduced as-is from the reference, where ClientGroup keys mConns by
+ *             CConn::BuildKey(addr) (a decimal number or a socket path) while OnRecvConvRst asks for
+ *             "conv:..." (callbacks/ConnReset.cpp:67-77; the reference's own todo at server/SubGroup.cpp:38
+ *             names the mismatch).
+ *   else      conv_row NONE.  The key fields (conv, dst, id, ctl_arg) of a packet that is not looked up
+ *             are never read.
+ * unknown[i] (optional status column) = RSK_RECV_VALID iff examined and not found, else RSK_RECV_DROP;
+ * *n_unknown is written, not accumulated.  rsk_demux_batch(status = unknown, ..., RSK_DEMUX_ID |
+ * RSK_DEMUX_DST | RSK_DEMUX_CONV) lists the distinct new keys in first-arrival order in seg_first: the
+ * order SubGroup::newConn makes them on a server.
+ * Messages (out->msgs; n_msg required with any array, arrays of n entries): one per unknown packet,
+ * order-stable, in packet order: cmd RSK_CMD_CONV_RST, body = conv, pay_len 4 (encode_uint32), pay_off 8k,
+ * id = the packet's IdBuf (zeros without an id column), src = i, avoid_key 0 (doSendCmd -> Send ->
+ * doSend(..., 0)) -- an rsk_encode_in as they stand.  This is the client's per-packet SendConvRst; a
+ * server, which creates a conv instead, leaves the messages out.  *n_msg = *n_unknown.
+ * SNAPSHOT SEMANTICS, as rsk_control_batch: every lookup sees the table as last indexed; a packet at or
+ * before its row's rst_first gets what the reference gives it, and rst_first lets the caller redo the
+ * tail; a conv the host creates from `unknown` exists from the next rebuild on.
+ * Launches: without a list or a count, memset nodes and one kernel.  With msgs / n_unknown the kernel
+ * also leaves its tile's number of unknown packets in the control path's per-stream scratch (sized by
+ * rsk_reserve_stream), one block scans them, and a third launch writes the list from conv_row's verdicts
+ * (the probes run once; the count cannot precede them as in rsk_control_batch, since a message here
+ * depends on a lookup).  A linear chain; no block waits on another.  n == 0 zeroes the given counts and
+ * fills a given rst_first.
+ * RSK_EINVAL: a NULL ctx, tab, in or out; a table a lookup cannot use (NULL state, conv or index; dst or
+ * id missing with its flag; unknown flags; bad capacity); with n > 0 a NULL status, conv or conv_row, or
+ * dst / id missing in `in` with the flag; an id column (the table's with BY_ID, in->id, msgs.id) that is
+ * not 8-B aligned; ctl_kind and ctl_arg not both set or both NULL; a message array without n_msg;
+ * n > RSK_MAX_BATCH. */
+typedef struct rsk_conv_resolve_in {
+    const int8_t   *status;   /* [n] dec->status */
+    const uint8_t  *cmd;      /* [n] dec->cmd, or NULL = all DATA */
+    const uint8_t  *hit;      /* [n] rsk_conn_resolve_batch's hit, or NULL = every packet reached its group */
+    const uint8_t  *id;       /* [n*8] dec->id, 8-B aligned; required with BY_ID, else only copied to the messages */
+    const uint32_t *conv;     /* [n] dec->conv */
+    const uint32_t *dst;      /* [n] the parse's TcpInfo dst; required with BY_DST */
+    const uint8_t  *ctl_kind; /* [n] rsk_control_batch's kind, or NULL */
+    const uint64_t *ctl_arg;  /* [n] rsk_control_batch's arg, or NULL */
+} rsk_conv_resolve_in;
+typedef struct rsk_conv_resolve_out {
+    uint32_t *conv_row;   /* [n] row, or RSK_CONN_NONE */
+    int8_t   *unknown;    /* [n] optional */
+    uint32_t *n_unknown;  /* [1] optional, written */
+    uint32_t *rst_first;  /* [capacity] optional */
+    rsk_ctl_msgs msgs;    /* m = n; optional */
+} rsk_conv_resolve_out;
+int rsk_conv_resolve_batch(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t n, const rsk_conv_resolve_in *in,
+                           const rsk_conv_resolve_out *out, void *stream);
+
+/* Send: SubGroup::sconnSend / ClientGroup::cconSend set the head's conv, then IConn::Send -> afterSend
+ * counts the packet.  ok[i] (optional) = 1 iff conv_row[i] < capacity and the row is LIVE; the given
+ * columns conv[i], dst[i], id[8i..] (an rsk_encode_in's) receive the row's values, or zero; *n_bad = the
+ * packets that are not ok (written).  With `sent` given (int32 [n], the encode's status) every packet
+ * that is ok and has sent[i] > 0 adds 1 to cur_out[row], combined on chip as the resolve's counts; no
+ * counting without it.  The caller expands before the encode (sent NULL) and counts after it (no output
+ * columns).  No scratch: memset nodes and one kernel.
+ * RSK_EINVAL: a NULL ctx, tab, out or tab->state; unknown flags or a bad capacity; a NULL conv_row with
+ * n > 0; an output column whose table column is NULL; sent without tab->cur_out; an id column (the
+ * table's or out->id) that is not 8-B aligned when out->id is given; n > RSK_MAX_BATCH. */
+typedef struct rsk_conv_send_out {  /* every field optional */
+    uint32_t *conv;   /* [n] */
+    uint32_t *dst;    /* [n] */
+    uint8_t  *id;     /* [n*8], 8-B aligned */
+    uint8_t  *ok;     /* [n] */
+    uint32_t *n_bad;  /* [1] */
+} rsk_conv_send_out;
+int rsk_conv_send_batch(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t n, const uint32_t *conv_row,
+                        const int32_t *sent, const rsk_conv_send_out *out, void *stream);
+
+/* IGroup::Flush (conn/IGroup.cpp:81-107) as one pass over the rows.  Per row r:
+ *   1. not LIVE: nothing but state[r] is read or written;
+ *   2. LIVE and alive[r] == 0: r is appended to dead_rows and its counters are left alone (the reference
+ *      closes it before the flush loop, so it is never flushed);
+ *   3. LIVE and alive: alive[r] = (prev_in[r] != cur_in[r]) && (prev_out[r] != cur_out[r]), then
+ *      prev_in[r] = cur_in[r], prev_out[r] = cur_out[r] (DataStat::Flush).
+ * dead_rows is in row order; *n_dead and *n_alive (the LIVE rows alive after the pass: IGroup::Alive() is
+ * n_alive != 0) are written, not accumulated.  A conv that goes quiet is therefore marked at one flush
+ * and listed at the next, as in the reference.  state stays read-only: the host clears LIVE for the
+ * rows it closes and rebuilds.  No index is read.  Launches and scratch are rsk_keepalive_flush's.
+ * RSK_EINVAL: a NULL ctx, tab, out, state, alive or one of the four counter columns; unknown flags or a
+ * bad capacity; dead_rows without n_dead. */
+typedef struct rsk_conv_flush_out {  /* every field optional */
+    uint32_t *dead_rows;  /* [C] */
+    uint32_t *n_dead;     /* [1] required with dead_rows */
+    uint32_t *n_alive;    /* [1] */
+} rsk_conv_flush_out;
+int rsk_conv_flush(rsk_ctx *ctx, const rsk_conv_table *tab, const rsk_conv_flush_out *out, void *stream);
+
+/* Host twins (host pointers, the same rules and outputs, nthreads as rsk_deliver_host; the IdBuf columns
+ * are read bytewise at any alignment; the build, the flush and the counting run on the caller's thread). */
+int rsk_conv_index_build_host(const rsk_conv_table *tab, uint32_t *n_dup, int nthreads);
+int rsk_conv_resolve_host(const rsk_conv_table *tab, uint32_t n, const rsk_conv_resolve_in *in,
+                          const rsk_conv_resolve_out *out, int nthreads);
+int rsk_conv_send_host(const rsk_conv_table *tab, uint32_t n, const uint32_t *conv_row, const int32_t *sent,
+                       const rsk_conv_send_out *out, int nthreads);
+int rsk_conv_flush_host(const rsk_conv_table *tab, const rsk_conv_flush_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

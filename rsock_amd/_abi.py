@@ -52,6 +52,7 @@ CONN_LIVE, CONN_ALIVE, CONN_NEW = 0x1, 0x2, 0x4
 KA_NONE = 0xFF
 KA_REQUEST_DELAY_MS = 15000
 KA_MAX_RETRY = 3
+CONV_BY_DST, CONV_BY_ID = 0x1, 0x2
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -190,6 +191,29 @@ class KeepaliveOut(ctypes.Structure):
     _fields_ = [("msgs", CtlMsgs), ("dead_rows", _vp), ("n_dead", _vp)]
 
 
+class ConvTable(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("state", _vp), ("conv", _vp), ("dst", _vp),
+                ("id", _vp), ("cur_in", _vp), ("cur_out", _vp), ("prev_in", _vp), ("prev_out", _vp), ("alive", _vp),
+                ("index", _vp)]
+
+
+class ConvResolveIn(ctypes.Structure):
+    _fields_ = [("status", _vp), ("cmd", _vp), ("hit", _vp), ("id", _vp), ("conv", _vp), ("dst", _vp),
+                ("ctl_kind", _vp), ("ctl_arg", _vp)]
+
+
+class ConvResolveOut(ctypes.Structure):
+    _fields_ = [("conv_row", _vp), ("unknown", _vp), ("n_unknown", _vp), ("rst_first", _vp), ("msgs", CtlMsgs)]
+
+
+class ConvSendOut(ctypes.Structure):
+    _fields_ = [("conv", _vp), ("dst", _vp), ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
+
+
+class ConvFlushOut(ctypes.Structure):
+    _fields_ = [("dead_rows", _vp), ("n_dead", _vp), ("n_alive", _vp)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -279,6 +303,20 @@ SIGNATURES = [
      [ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ControlIn), ctypes.POINTER(ControlOut), ctypes.c_int]),
     ("rsk_keepalive_flush_host", ctypes.c_int,
      [ctypes.POINTER(ConnTable), ctypes.POINTER(Keepalive), ctypes.POINTER(KeepaliveOut), ctypes.c_int]),
+    ("rsk_conv_index_build", ctypes.c_int, [_vp, ctypes.POINTER(ConvTable), _vp, _vp]),
+    ("rsk_conv_resolve_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConvTable), ctypes.c_uint32, ctypes.POINTER(ConvResolveIn), ctypes.POINTER(ConvResolveOut),
+      _vp]),
+    ("rsk_conv_send_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConvTable), ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ConvSendOut), _vp]),
+    ("rsk_conv_flush", ctypes.c_int, [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvFlushOut), _vp]),
+    ("rsk_conv_index_build_host", ctypes.c_int, [ctypes.POINTER(ConvTable), _vp, ctypes.c_int]),
+    ("rsk_conv_resolve_host", ctypes.c_int,
+     [ctypes.POINTER(ConvTable), ctypes.c_uint32, ctypes.POINTER(ConvResolveIn), ctypes.POINTER(ConvResolveOut),
+      ctypes.c_int]),
+    ("rsk_conv_send_host", ctypes.c_int,
+     [ctypes.POINTER(ConvTable), ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ConvSendOut), ctypes.c_int]),
+    ("rsk_conv_flush_host", ctypes.c_int, [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvFlushOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

@@ -499,6 +499,125 @@ def keepalive_flush_host(tab: ConnTable, ka_tries, established_ms, now_ms: int, 
         raise RskError(f"rsk_keepalive_flush_host failed: rc={rc}")
 
 
+_CONV_COLUMNS = (("state", torch.uint8, 1), ("conv", torch.int32, 1), ("dst", torch.int32, 1), ("id", torch.uint8, 8),
+                 ("cur_in", torch.int32, 1), ("cur_out", torch.int32, 1), ("prev_in", torch.int32, 1),
+                 ("prev_out", torch.int32, 1), ("alive", torch.uint8, 1))
+
+
+@dataclass
+class ConvTable:
+    """The conv table (rsk_conv_table): a group's convs at the app level -- a server's SubGroups
+    (by_dst and by_id), a ClientGroup's mConvMap (neither) -- with the DataStat words of each, in columns
+    of torch tensors (signed storage of the unsigned C types) plus the opaque index.  Shaped like
+    ConnTable: on a device the batch calls of Codec take it, on "cpu" the host twins below; after any
+    change to state, conv, dst or id call rebuild().  A column set to None is passed as NULL (cur_in
+    None: the resolve does not count)."""
+
+    capacity: int
+    by_dst: bool
+    by_id: bool
+    state: torch.Tensor          # uint8: CONN_LIVE
+    conv: torch.Tensor
+    dst: torch.Tensor | None     # by_dst only
+    id: torch.Tensor | None      # capacity * 8 bytes; by_id only
+    cur_in: torch.Tensor | None
+    cur_out: torch.Tensor | None
+    prev_in: torch.Tensor | None
+    prev_out: torch.Tensor | None
+    alive: torch.Tensor | None   # uint8; set to 1 when a row is created
+    index: torch.Tensor          # opaque, rsk_conn_index_bytes(capacity, 0) bytes
+
+    @classmethod
+    def alloc(cls, capacity: int, device, by_dst: bool = False, by_id: bool = False) -> "ConvTable":
+        nbytes = lib().rsk_conn_index_bytes(capacity, 0)
+        if nbytes == 0:
+            raise RskError(f"rsk_conn_index_bytes: bad capacity {capacity}")
+        cols = {name: torch.zeros(capacity * k, dtype=dt, device=device) for name, dt, k in _CONV_COLUMNS}
+        if not by_dst:
+            cols["dst"] = None
+        if not by_id:
+            cols["id"] = None
+        return cls(capacity=int(capacity), by_dst=bool(by_dst), by_id=bool(by_id),
+                   index=torch.empty(nbytes // 4, dtype=torch.int32, device=device), **cols)
+
+    @property
+    def flags(self) -> int:
+        return (_abi.CONV_BY_DST if self.by_dst else 0) | (_abi.CONV_BY_ID if self.by_id else 0)
+
+    def abi(self) -> _abi.ConvTable:
+        return _abi.ConvTable(self.capacity, self.flags, *[_ptr(getattr(self, name)) for name, _, _ in _CONV_COLUMNS],
+                              _ptr(self.index))
+
+    def load(self, **cols) -> "ConvTable":
+        """Copy numpy arrays (any integer dtype of the column's width) into the named columns."""
+        for name, a in cols.items():
+            t = getattr(self, name)
+            a = np.ascontiguousarray(a)
+            t.copy_(torch.from_numpy(a.view(f"i{a.dtype.itemsize}" if t.dtype != torch.uint8 else np.uint8)))
+        return self
+
+    def to(self, device) -> "ConvTable":
+        """A copy of every column and of the index on `device` (the index is valid on either side)."""
+        mv = lambda t: None if t is None else t.to(device, copy=True)  # noqa: E731
+        return ConvTable(self.capacity, self.by_dst, self.by_id, *[mv(getattr(self, name)) for name, _, _ in _CONV_COLUMNS],
+                         mv(self.index))
+
+    def column(self, name: str) -> np.ndarray:
+        """A column on the host as its unsigned C type."""
+        a = getattr(self, name).cpu().numpy()
+        return a.view(f"u{a.dtype.itemsize}")
+
+    def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
+        """rsk_conv_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
+        table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
+        if (codec is None) != (self.index.device.type == "cpu"):
+            raise RskError("ConvTable.rebuild: a device table takes its Codec, a cpu table none")
+        if codec is None:
+            _check(lib().rsk_conv_index_build_host(ctypes.byref(self.abi()), _ptr(n_dup), 1),
+                   "rsk_conv_index_build_host")
+        else:
+            codec.conv_index_build(self, n_dup=n_dup, stream=stream)
+
+
+def _conv_resolve_structs(status, conv, conv_row, cmd, hit, id, dst, ctl_kind, ctl_arg, unknown, n_unknown, rst_first,
+                          msgs):
+    cin = _abi.ConvResolveIn(_addr(status), _addr(cmd), _addr(hit), _addr(id), _addr(conv), _addr(dst),
+                             _addr(ctl_kind), _addr(ctl_arg))
+    cout = _abi.ConvResolveOut(_addr(conv_row), _addr(unknown), _addr(n_unknown), _addr(rst_first),
+                               msgs.abi_msgs() if msgs is not None else _abi.CtlMsgs())
+    return cin, cout
+
+
+def conv_resolve_host(tab: ConvTable, status, conv, conv_row, cmd=None, hit=None, id=None, dst=None, ctl_kind=None,
+                      ctl_arg=None, unknown=None, n_unknown=None, rst_first=None, msgs: "ControlBuffers | None" = None,
+                      nthreads: int = 1) -> None:
+    """rsk_conv_resolve_host on a "cpu" ConvTable, with "cpu" tensors or numpy arrays of the C types'
+    widths (no GPU); the arguments of Codec.conv_resolve_batch."""
+    cin, cout = _conv_resolve_structs(status, conv, conv_row, cmd, hit, id, dst, ctl_kind, ctl_arg, unknown, n_unknown,
+                                      rst_first, msgs)
+    rc = lib().rsk_conv_resolve_host(ctypes.byref(tab.abi()), len(status), ctypes.byref(cin), ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conv_resolve_host failed: rc={rc}")
+
+
+def conv_send_host(tab: ConvTable, conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
+                   nthreads: int = 1) -> None:
+    """rsk_conv_send_host on a "cpu" ConvTable (no GPU); the arguments of Codec.conv_send_batch."""
+    sout = _abi.ConvSendOut(_addr(conv), _addr(dst), _addr(id), _addr(ok), _addr(n_bad))
+    rc = lib().rsk_conv_send_host(ctypes.byref(tab.abi()), len(conv_row), _addr(conv_row), _addr(sent), ctypes.byref(sout),
+                                  nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conv_send_host failed: rc={rc}")
+
+
+def conv_flush_host(tab: ConvTable, dead_rows=None, n_dead=None, n_alive=None, nthreads: int = 1) -> None:
+    """rsk_conv_flush_host on a "cpu" ConvTable (no GPU); the arguments of Codec.conv_flush."""
+    fout = _abi.ConvFlushOut(_addr(dead_rows), _addr(n_dead), _addr(n_alive))
+    rc = lib().rsk_conv_flush_host(ctypes.byref(tab.abi()), ctypes.byref(fout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conv_flush_host failed: rc={rc}")
+
+
 @dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
@@ -862,6 +981,48 @@ class Codec:
         ka = _abi.Keepalive(_addr(ka_tries), _addr(established_ms), now_ms, request_delay_ms, max_retry, int(online))
         _check(lib().rsk_keepalive_flush(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(ka),
                                          ctypes.byref(out.abi_flush()), _stream(stream)), "rsk_keepalive_flush")
+
+    def conv_index_build(self, tab: "ConvTable", n_dup=None, stream=None) -> None:
+        """rsk_conv_index_build: rebuild tab.index from its state, conv (dst, id) columns; n_dup [1] gets
+        the LIVE rows that lost their key to a lower row."""
+        _check(lib().rsk_conv_index_build(self._ctx, ctypes.byref(tab.abi()), _ptr(n_dup), _stream(stream)),
+               "rsk_conv_index_build")
+
+    def conv_resolve_batch(self, tab: "ConvTable", status, conv, conv_row, cmd=None, hit=None, id=None, dst=None,
+                           ctl_kind=None, ctl_arg=None, unknown=None, n_unknown=None, rst_first=None,
+                           msgs: "ControlBuffers | None" = None, stream=None) -> None:
+        """SubGroup::OnRecv's / ClientGroup::OnRecv's lookup for n decoded packets (rsk_conv_resolve_batch):
+        conv_row[i] = the LIVE row of packet i's (id, dst, conv) -- each part only with the table's flag --
+        or CONN_NONE; examined iff status[i] == RECV_VALID, cmd[i] == CMD_DATA (cmd None: all DATA) and
+        hit[i] (the conn resolve's; None: all).  Every examined packet that found its row adds 1 to
+        tab.cur_in[row], exactly, whatever the skew.  With ctl_kind / ctl_arg (control_batch's kind / arg)
+        a CTL_CONV_RST packet is looked up by the conv in its body on a by_dst table; rst_first
+        [capacity] gets the first such packet per row.  unknown is a status column of the examined
+        packets that found no row (feed it to demux_batch for the distinct new keys), n_unknown [1]
+        their number; with msgs (a ControlBuffers) one CONV_RST message per unknown packet lands in
+        msgs.msg_* in packet order, msgs.n_msg of them.  Lookups see the table as last indexed."""
+        cin, cout = _conv_resolve_structs(status, conv, conv_row, cmd, hit, id, dst, ctl_kind, ctl_arg, unknown,
+                                          n_unknown, rst_first, msgs)
+        _check(lib().rsk_conv_resolve_batch(self._ctx, ctypes.byref(tab.abi()), status.numel(), ctypes.byref(cin),
+                                            ctypes.byref(cout), _stream(stream)), "rsk_conv_resolve_batch")
+
+    def conv_send_batch(self, tab: "ConvTable", conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
+                        stream=None) -> None:
+        """The send side of the conv table (rsk_conv_send_batch): the given columns conv / dst / id (an
+        encode's) get row conv_row[i]'s values, or zero with ok[i] = 0 when the row is out of range or
+        not LIVE; n_bad [1] counts those.  With sent (int32, the encode's status) every ok packet with
+        sent[i] > 0 adds 1 to tab.cur_out[row].  Expand before the encode (sent None), count after it."""
+        sout = _abi.ConvSendOut(_ptr(conv), _ptr(dst), _ptr(id), _ptr(ok), _ptr(n_bad))
+        _check(lib().rsk_conv_send_batch(self._ctx, ctypes.byref(tab.abi()), conv_row.numel(), _ptr(conv_row), _ptr(sent),
+                                         ctypes.byref(sout), _stream(stream)), "rsk_conv_send_batch")
+
+    def conv_flush(self, tab: "ConvTable", dead_rows=None, n_dead=None, n_alive=None, stream=None) -> None:
+        """IGroup::Flush as one pass over the rows of `tab` (rsk_conv_flush): a LIVE row whose alive is 0
+        is listed in dead_rows (row order, n_dead [1]); every other LIVE row gets alive = (prev_in !=
+        cur_in and prev_out != cur_out) and prev = cur.  n_alive [1] = the LIVE rows alive afterwards."""
+        fout = _abi.ConvFlushOut(_ptr(dead_rows), _ptr(n_dead), _ptr(n_alive))
+        _check(lib().rsk_conv_flush(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(fout), _stream(stream)),
+               "rsk_conv_flush")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

@@ -2,10 +2,8 @@
 // INetGroup's map from connKey to INetConn (conn/INetGroup.cpp:57-83) as an open-addressing index over
 // caller-owned columns, and the TcpInfo of each FakeTcp (conn/FakeTcp.cpp:14-50) as those columns.
 //
-//   k_conn_build    launched twice per rebuild: <0> clears the index with 16-B stores, <1> inserts the
-//                   LIVE rows, one lane per row and one CAS per probe step; a row that meets an entry
-//                   with its own key leaves the lower row there (atomicMin), so the lowest row of a key
-//                   wins whatever order the lanes ran in, and exactly one row loses per meeting.
+//   k_index_build   (rsk_conn_dev.h, shared with the conv table through the accessor) launched twice per
+//                   rebuild: clear the index, then insert the LIVE rows; the lowest row of a key wins.
 //   k_conn_resolve  one lane per packet and step, 8 steps per block; the probe runs through global memory
 //                   (the index and the key column of a table of rsock's size stay in L2).
 //   k_conn_expand   one lane per packet; a gather from the row's columns, every output column stored
@@ -23,56 +21,11 @@ using rsk::dev_tab;
 using rsk::gptr;
 using rsk::tab_lookup_ok;
 using rsk::tab_ok;
+using rsk::wave_count;
 using rsk::zero_word;
 
 constexpr unsigned kBlock = 256;  // threads per block
 static_assert((uint64_t)RSK_MAX_BATCH + 8u * kBlock - 1u <= 0xFFFFFFFFull, "the block counts are computed in 32 bits");
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// One atomic per wave for a count of lanes (the word was zeroed on the stream ahead of the launch).
-__device__ __forceinline__ void wave_count(uint32_t *word, bool mine) {
-    const uint32_t cnt = (uint32_t)__popcll(__ballot(mine));
-    if (cnt && (threadIdx.x & 63u) == 0u) atomicAdd(word, cnt);
-}
-
-struct BuildArgs {
-    DevConnTab t;
-    uint32_t *index;
-    const uint8_t *state;
-    uint32_t *n_dup;
-    uint32_t capacity, slots;
-    bool by_id;
-};
-
-template <int PHASE>
-__global__ __launch_bounds__(kBlock) void k_conn_build(BuildArgs a) {
-    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
-    if (PHASE == 0) {  // slots is a multiple of 4 and the index 16-B aligned
-        const u32x4 empty = {rsk::kConnEmpty, rsk::kConnEmpty, rsk::kConnEmpty, rsk::kConnEmpty};
-        if (g < a.slots / 4u) reinterpret_cast<RSK_GLOBAL u32x4 *>(gptr(a.index))[g] = empty;
-        return;
-    }
-    bool dup = false;
-    if (g < a.capacity && (gptr(a.state)[g] & RSK_CONN_LIVE)) {
-        const uint64_t key = a.t.key(g), id = a.by_id ? a.t.id(g) : 0ull;
-        uint32_t s = rsk::conn_home(key, id, a.slots);
-        // at most `capacity` entries are ever taken and slots >= 2 capacity: a free entry is met within
-        // `slots` steps; the bound only keeps a corrupted launch from spinning
-        for (uint32_t step = 0; step < a.slots; ++step, s = rsk::conn_next(s, a.slots)) {
-            const uint32_t e = atomicCAS(a.index + s, rsk::kConnEmpty, g);
-            if (e == rsk::kConnEmpty) break;  // the entry was free and is now this row's
-            // e is a row of this build (the clear ran before this launch), and an entry's key never
-            // changes once taken: only rows of the same key replace each other in it
-            if (e < a.capacity && a.t.key(e) == key && (!a.by_id || a.t.id(e) == id)) {
-                atomicMin(a.index + s, g);  // one of the two rows stays: the other is the duplicate
-                dup = true;
-                break;
-            }
-        }
-    }
-    if (a.n_dup) wave_count(a.n_dup, dup);
-}
 
 struct ResolveArgs {
     DevConnTab t;
@@ -195,19 +148,8 @@ extern "C" int rsk_conn_index_build(rsk_ctx *c, const rsk_conn_table *t, uint32_
     if ((t->flags & RSK_CONN_BY_ID) && (reinterpret_cast<uintptr_t>(t->id) & 7u)) return RSK_EINVAL;
     rsk::DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    if (int r = zero_word(n_dup, s)) return r;
-    BuildArgs a;
-    a.t = dev_tab(t);
-    a.index = t->index;
-    a.state = t->state;
-    a.n_dup = n_dup;
-    a.capacity = t->capacity;
-    a.slots = rsk::conn_slots(t->capacity);
-    a.by_id = (t->flags & RSK_CONN_BY_ID) != 0;
-    hipLaunchKernelGGL(k_conn_build<0>, dim3((a.slots / 4u + kBlock - 1u) / kBlock), dim3(kBlock), 0, s, a);
-    hipLaunchKernelGGL(k_conn_build<1>, dim3((a.capacity + kBlock - 1u) / kBlock), dim3(kBlock), 0, s, a);
-    return rsk::launch_check("k_conn_build");
+    return rsk::index_build(dev_tab(t), t->index, t->state, t->capacity, (t->flags & RSK_CONN_BY_ID) != 0, n_dup,
+                            (hipStream_t)stream);
 }
 
 extern "C" int rsk_conn_resolve_batch(rsk_ctx *c, const rsk_conn_table *t, uint32_t n, const rsk_conn_resolve_in *in,

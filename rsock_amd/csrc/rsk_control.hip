@@ -8,7 +8,7 @@
 // Both entry points are reduce-then-scan over tiles, three launches in a linear chain:
 //   k_ctl_count / k_ka_count   per tile, the number of list entries its items will make (through LDS, one
 //                              plain store per block: no atomics);
-//   k_tile_scan                one block: exclusive scan of the tile counts in place, the totals to the
+//   k_tile_scan (rsk_tile_dev.h, shared with rsk_conv.hip)   one block: exclusive scan of the tile counts in place, the totals to the
 //                              caller's count words;
 //   k_ctl_main / k_ka_main     the work itself; every item's list position = its tile's base + its rank
 //                              inside the tile.
@@ -19,111 +19,30 @@
 // addresses, every step's loads are issued before the probes.
 #include <hip/hip_runtime.h>
 
-#include "rsk_conn_dev.h"
+#include "rsk_tile_dev.h"
 
 namespace {
 
 using rsk::DevConnTab;
 using rsk::funnel;
 using rsk::gptr;
+using rsk::k_tile_scan;
+using rsk::kScanBlock;
+using rsk::memset_async;
+using rsk::misaligned8;
+using rsk::msg_out;
+using rsk::MsgOut;
+using rsk::msgs_any;
+using rsk::put_msg;
+using rsk::tile_positions;
+using rsk::u32x2;
 
-constexpr unsigned kBlock = 256;
-constexpr unsigned kWaves = kBlock / 64u;
+constexpr unsigned kBlock = rsk::kTileBlock;
+constexpr unsigned kWaves = rsk::kTileWaves;
 constexpr unsigned kCtlPer = 8;  // packets per thread: the resolve's tile
 constexpr unsigned kKaPer = 4;   // rows per thread
 static_assert(kBlock * kCtlPer == rsk::kControlTile && kBlock * kKaPer == rsk::kFlushTile,
               "scratch size (rsk_ctx.h) and tile sizes must agree");
-constexpr unsigned kScanBlock = 1024;  // threads of the one block that scans the tile counts
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // a tile's two counts
-
-// The message columns as the kernels write them (rsk_ctl_msgs; id as one word per entry).
-struct MsgOut {
-    uint8_t *cmd;
-    uint64_t *body;
-    uint64_t *id;
-    uint32_t *src;
-    uint64_t *avoid;
-    uint64_t *pay_off;
-    uint16_t *pay_len;
-};
-
-__device__ __forceinline__ void put_msg(const MsgOut &m, uint32_t k, uint32_t cmd, uint64_t body, uint64_t id,
-                                        uint32_t src, uint64_t avoid) {
-    if (m.cmd) gptr(m.cmd)[k] = (uint8_t)cmd;
-    if (m.body) gptr(m.body)[k] = body;
-    if (m.id) gptr(m.id)[k] = id;
-    if (m.src) gptr(m.src)[k] = src;
-    if (m.avoid) gptr(m.avoid)[k] = avoid;
-    if (m.pay_off) gptr(m.pay_off)[k] = 8ull * k;
-    if (m.pay_len) gptr(m.pay_len)[k] = (uint16_t)8;
-}
-
-// List positions of a tile's flagged items in item order: item (k, t) of the tile is its k * 256 + t-th.
-// pos[k] = base + the number of flagged items before (k, this thread); cnt: PER * kWaves words of LDS.
-// Returns the tile's number of flagged items.  Every thread of the block must call it.
-template <unsigned PER>
-__device__ __forceinline__ uint32_t tile_positions(const bool (&flag)[PER], uint32_t base, uint32_t (*cnt)[kWaves],
-                                                   uint32_t (&pos)[PER]) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t below[PER];
-#pragma unroll
-    for (unsigned k = 0; k < PER; ++k) {
-        const uint64_t b = __ballot(flag[k]);
-        below[k] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0u) cnt[k][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    uint32_t run = 0;
-#pragma unroll
-    for (unsigned k = 0; k < PER; ++k) {
-#pragma unroll
-        for (unsigned w = 0; w < kWaves; ++w) {
-            if (w == wave) pos[k] = base + run + below[k];
-            run += cnt[k][w];
-        }
-    }
-    return run;
-}
-
-// Exclusive scan of the nt tile counts (both components) in place, one block; the totals go to
-// tile[nt] and to *tot_x / *tot_y (each may be NULL).  Each thread owns ceil(nt / kScanBlock)
-// consecutive tiles.  A component's total is at most the number of items (< 2^32).
-__global__ __launch_bounds__(kScanBlock) void k_tile_scan(u32x2 *tile, uint32_t nt, uint32_t *tot_x, uint32_t *tot_y) {
-    __shared__ u32x2 part[kScanBlock];
-    const uint32_t per = (nt + kScanBlock - 1u) / kScanBlock;
-    const uint32_t lo = threadIdx.x * per < nt ? threadIdx.x * per : nt;
-    const uint32_t hi = lo + per < nt ? lo + per : nt;
-    RSK_GLOBAL u32x2 *ts = gptr(tile);
-    u32x2 s = u32x2{0u, 0u};
-    for (uint32_t t = lo; t < hi; ++t) {
-        const u32x2 v = ts[t];
-        s.x += v.x;
-        s.y += v.y;
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (unsigned d = 1; d < kScanBlock; d <<= 1) {  // Hillis-Steele inclusive scan of the per-thread sums
-        const u32x2 v = threadIdx.x >= d ? part[threadIdx.x - d] : u32x2{0u, 0u};
-        __syncthreads();
-        part[threadIdx.x].x += v.x;
-        part[threadIdx.x].y += v.y;
-        __syncthreads();
-    }
-    u32x2 run = u32x2{part[threadIdx.x].x - s.x, part[threadIdx.x].y - s.y};
-    for (uint32_t t = lo; t < hi; ++t) {
-        const u32x2 v = ts[t];
-        ts[t] = run;
-        run.x += v.x;
-        run.y += v.y;
-    }
-    if (threadIdx.x == kScanBlock - 1u) {
-        const u32x2 tot = part[kScanBlock - 1u];
-        ts[nt] = tot;
-        if (tot_x) *gptr(tot_x) = tot.x;
-        if (tot_y) *gptr(tot_y) = tot.y;
-    }
-}
 
 // ---- rsk_control_batch ---------------------------------------------------------------------------------
 struct CtlArgs {
@@ -287,9 +206,9 @@ __global__ __launch_bounds__(kBlock) void k_ctl_main(CtlArgs a) {
         const uint32_t i = (uint32_t)(base + k * kBlock);
         if (kind[k] == RSK_CTL_KA_REQ) {
             const bool hit = row[k] != RSK_CONN_NONE;
-            put_msg(a.m, pos[k], hit ? RSK_CMD_KEEP_ALIVE_RESP : RSK_CMD_NETCONN_RST, arg[k], idw[k], i, hit ? 0ull : arg[k]);
+            put_msg(a.m, pos[k], hit ? RSK_CMD_KEEP_ALIVE_RESP : RSK_CMD_NETCONN_RST, arg[k], idw[k], i, hit ? 0ull : arg[k], 8u);
         } else {
-            put_msg(a.m, pos[k], RSK_CMD_NETCONN_RST, ck[k], idw[k], i, ck[k]);
+            put_msg(a.m, pos[k], RSK_CMD_NETCONN_RST, ck[k], idw[k], i, ck[k], 8u);
         }
     }
 }
@@ -395,23 +314,9 @@ __global__ __launch_bounds__(kBlock) void k_ka_main(KaArgs a) {
         const uint32_t r = blockIdx.x * rsk::kFlushTile + k * kBlock + threadIdx.x;
         // a row makes one entry per list at most, so a position is below the capacity
         if (emit[k] && pe[k] < a.capacity)
-            put_msg(a.m, pe[k], RSK_CMD_KEEP_ALIVE_REQ, gptr(a.conn_key)[r], a.ids ? gptr(a.ids)[r] : 0ull, r, 0ull);
+            put_msg(a.m, pe[k], RSK_CMD_KEEP_ALIVE_REQ, gptr(a.conn_key)[r], a.ids ? gptr(a.ids)[r] : 0ull, r, 0ull, 8u);
         if (dead[k] && a.dead_rows && pd[k] < a.capacity) gptr(a.dead_rows)[pd[k]] = r;
     }
-}
-
-bool msgs_any(const rsk_ctl_msgs &m) {
-    return m.cmd || m.body || m.id || m.src || m.avoid_key || m.pay_off || m.pay_len;
-}
-MsgOut msg_out(const rsk_ctl_msgs &m) {
-    return MsgOut{m.cmd, m.body, reinterpret_cast<uint64_t *>(m.id), m.src, m.avoid_key, m.pay_off, m.pay_len};
-}
-bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
-
-int memset_async(void *p, int v, size_t bytes, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(p, v, bytes, s);
-    if (e != hipSuccess) { rsk::set_error("hipMemsetAsync", e); return RSK_EDEVICE; }
-    return RSK_OK;
 }
 
 }  // namespace

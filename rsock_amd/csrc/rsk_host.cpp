@@ -3,7 +3,7 @@
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
 // (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
 // (rsk_conn_*_host) with its control packets and keepalive timer (rsk_control_host,
-// rsk_keepalive_flush_host); the single-frame slot staging, the capture filter's text form and the connection
+// rsk_keepalive_flush_host) and of the conv table (rsk_conv_*_host); the single-frame slot staging, the capture filter's text form and the connection
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
@@ -198,6 +198,25 @@ bool conn_tab_lookup_ok(const rsk_conn_table *t) {
     return conn_tab_ok(t) && t->conn_key && t->index && (!(t->flags & RSK_CONN_BY_ID) || t->id);
 }
 
+// The index of any table whose accessor T gives key(row) and id(row): rows in increasing order, so the
+// first row of a key takes its entry and every later one is a duplicate.
+template <typename T>
+void index_build_host(const T &h, uint32_t *index, const uint8_t *state, uint32_t capacity, bool by_id, uint32_t *n_dup) {
+    const uint32_t slots = rsk::conn_slots(capacity);
+    std::memset(index, 0xFF, 4ull * slots);
+    uint32_t dup = 0;
+    for (uint32_t r = 0; r < capacity; ++r) {
+        if (!(state[r] & RSK_CONN_LIVE)) continue;
+        const uint64_t key = h.key(r), id = by_id ? h.id(r) : 0ull;
+        for (uint32_t s = rsk::conn_home(key, id, slots);; s = rsk::conn_next(s, slots)) {
+            const uint32_t e = index[s];
+            if (e == rsk::kConnEmpty) { index[s] = r; break; }
+            if (h.key(e) == key && (!by_id || h.id(e) == id)) { ++dup; break; }
+        }
+    }
+    if (n_dup) *n_dup = dup;
+}
+
 }  // namespace
 
 extern "C" uint64_t rsk_conn_index_bytes(uint32_t capacity, uint32_t flags) {
@@ -205,25 +224,10 @@ extern "C" uint64_t rsk_conn_index_bytes(uint32_t capacity, uint32_t flags) {
     return 4ull * rsk::conn_slots(capacity);
 }
 
-// Rows in increasing order, so the first row of a key takes its entry and every later one is a duplicate.
 extern "C" int rsk_conn_index_build_host(const rsk_conn_table *t, uint32_t *n_dup, int /*nthreads*/) {
     if (!conn_tab_lookup_ok(t) || !t->state) return RSK_EINVAL;
     if (reinterpret_cast<uintptr_t>(t->index) & 15u) return RSK_EINVAL;
-    const uint32_t slots = rsk::conn_slots(t->capacity);
-    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
-    const HostConnTab h{t};
-    std::memset(t->index, 0xFF, 4ull * slots);
-    uint32_t dup = 0;
-    for (uint32_t r = 0; r < t->capacity; ++r) {
-        if (!(t->state[r] & RSK_CONN_LIVE)) continue;
-        const uint64_t key = h.key(r), id = by_id ? h.id(r) : 0ull;
-        for (uint32_t s = rsk::conn_home(key, id, slots);; s = rsk::conn_next(s, slots)) {
-            const uint32_t e = t->index[s];
-            if (e == rsk::kConnEmpty) { t->index[s] = r; break; }
-            if (h.key(e) == key && (!by_id || h.id(e) == id)) { ++dup; break; }
-        }
-    }
-    if (n_dup) *n_dup = dup;
+    index_build_host(HostConnTab{t}, t->index, t->state, t->capacity, (t->flags & RSK_CONN_BY_ID) != 0, n_dup);
     return RSK_OK;
 }
 
@@ -442,6 +446,139 @@ extern "C" int rsk_keepalive_flush_host(const rsk_conn_table *t, const rsk_keepa
     }
     if (out->msgs.n_msg) *out->msgs.n_msg = n_msg;
     if (out->n_dead) *out->n_dead = n_dead;
+    return RSK_OK;
+}
+
+// ---- conv table (rsk_conv_table): the host twins; the index is the connection table's --------------------
+namespace {
+
+constexpr uint32_t kConvFlags = RSK_CONV_BY_DST | RSK_CONV_BY_ID;
+
+struct HostConvTab {
+    const rsk_conv_table *t;
+    uint32_t entry(uint32_t s) const { return t->index[s]; }
+    uint64_t key(uint32_t row) const {
+        const uint64_t c = t->conv[row];
+        return (t->flags & RSK_CONV_BY_DST) ? ((uint64_t)t->dst[row] << 32) | c : c;
+    }
+    uint64_t id(uint32_t row) const { return load64(t->id + 8ull * row); }
+};
+
+bool conv_tab_ok(const rsk_conv_table *t) {
+    return t && !(t->flags & ~kConvFlags) && t->capacity >= 1u && t->capacity <= RSK_CONN_MAX_ROWS;
+}
+bool conv_tab_lookup_ok(const rsk_conv_table *t) {
+    return conv_tab_ok(t) && t->state && t->conv && t->index && (!(t->flags & RSK_CONV_BY_DST) || t->dst) &&
+           (!(t->flags & RSK_CONV_BY_ID) || t->id);
+}
+
+}  // namespace
+
+extern "C" int rsk_conv_index_build_host(const rsk_conv_table *t, uint32_t *n_dup, int /*nthreads*/) {
+    if (!conv_tab_lookup_ok(t)) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(t->index) & 15u) return RSK_EINVAL;
+    index_build_host(HostConvTab{t}, t->index, t->state, t->capacity, (t->flags & RSK_CONV_BY_ID) != 0, n_dup);
+    return RSK_OK;
+}
+
+// The lookups over shards; then one walk in packet order for the counts, the resets' rows and the list.
+extern "C" int rsk_conv_resolve_host(const rsk_conv_table *t, uint32_t n, const rsk_conv_resolve_in *in,
+                                     const rsk_conv_resolve_out *out, int nthreads) {
+    if (!in || !out || !conv_tab_lookup_ok(t)) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONV_BY_ID) != 0, by_dst = (t->flags & RSK_CONV_BY_DST) != 0;
+    if (n && (!in->status || !in->conv || !out->conv_row || (by_dst && !in->dst) || (by_id && !in->id))) return RSK_EINVAL;
+    if ((in->ctl_kind == nullptr) != (in->ctl_arg == nullptr)) return RSK_EINVAL;
+    const bool list = ctl_msgs_any(out->msgs);
+    if (list && !out->msgs.n_msg) return RSK_EINVAL;
+    if (n > RSK_MAX_BATCH) return RSK_EINVAL;
+    if (out->rst_first) std::memset(out->rst_first, 0xFF, 4ull * t->capacity);
+    std::vector<uint8_t> mode(n);  // 0 not looked up, 1 DATA, 2 CONV_RST
+    uint8_t *md = mode.data();
+    const rsk_conv_resolve_in a = *in;
+    uint32_t *rows = out->conv_row;
+    const HostConvTab h{t};
+    const uint32_t cap = t->capacity;
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        for (uint32_t i = lo; i < hi; ++i) {
+            const bool ex = a.status[i] == RSK_RECV_VALID && (!a.cmd || a.cmd[i] == RSK_CMD_DATA) && (!a.hit || a.hit[i]);
+            const bool rst = !ex && a.ctl_kind && by_dst && a.ctl_kind[i] == RSK_CTL_CONV_RST;
+            uint32_t row = RSK_CONN_NONE;
+            if (ex || rst) {
+                uint64_t key = ex ? (uint64_t)a.conv[i] : (uint64_t)(uint32_t)a.ctl_arg[i];
+                if (by_dst) key |= (uint64_t)a.dst[i] << 32;
+                row = rsk::conn_lookup(h, cap, by_id, key, by_id ? load64(a.id + 8ull * i) : 0ull);
+            }
+            md[i] = ex ? 1 : rst ? 2 : 0;
+            rows[i] = row;
+        }
+    });
+    uint32_t n_unk = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t row = rows[i];
+        const bool unk = mode[i] == 1 && row == RSK_CONN_NONE;
+        if (out->unknown) out->unknown[i] = unk ? (int8_t)RSK_RECV_VALID : (int8_t)RSK_RECV_DROP;
+        if (row != RSK_CONN_NONE) {
+            if (mode[i] == 1 && t->cur_in) ++t->cur_in[row];
+            if (mode[i] == 2 && out->rst_first && out->rst_first[row] == 0xFFFFFFFFu) out->rst_first[row] = i;
+        }
+        if (unk) {
+            if (list) {
+                ctl_put_msg(out->msgs, n_unk, RSK_CMD_CONV_RST, in->conv[i], in->id ? in->id + 8ull * i : nullptr, i, 0ull);
+                if (out->msgs.pay_len) out->msgs.pay_len[n_unk] = 4;  // encode_uint32 (ConnReset.cpp:34-41)
+            }
+            ++n_unk;
+        }
+    }
+    if (out->msgs.n_msg) *out->msgs.n_msg = n_unk;
+    if (out->n_unknown) *out->n_unknown = n_unk;
+    return RSK_OK;
+}
+
+extern "C" int rsk_conv_send_host(const rsk_conv_table *t, uint32_t n, const uint32_t *conv_row, const int32_t *sent,
+                                  const rsk_conv_send_out *out, int /*nthreads*/) {
+    if (!out || !conv_tab_ok(t) || !t->state) return RSK_EINVAL;
+    if ((out->conv && !t->conv) || (out->dst && !t->dst) || (out->id && !t->id) || (sent && !t->cur_out)) return RSK_EINVAL;
+    if (n && !conv_row) return RSK_EINVAL;
+    if (n > RSK_MAX_BATCH) return RSK_EINVAL;
+    uint32_t bad = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t r = conv_row[i];
+        const bool ok = r < t->capacity && (t->state[r] & RSK_CONN_LIVE);
+        if (out->conv) out->conv[i] = ok ? t->conv[r] : 0u;
+        if (out->dst) out->dst[i] = ok ? t->dst[r] : 0u;
+        if (out->id) {
+            if (ok) std::memcpy(out->id + 8ull * i, t->id + 8ull * r, 8);
+            else std::memset(out->id + 8ull * i, 0, 8);
+        }
+        if (out->ok) out->ok[i] = ok;
+        bad += !ok;
+        if (ok && sent && sent[i] > 0) ++t->cur_out[r];  // IConn::Send -> afterSend
+    }
+    if (out->n_bad) *out->n_bad = bad;
+    return RSK_OK;
+}
+
+extern "C" int rsk_conv_flush_host(const rsk_conv_table *t, const rsk_conv_flush_out *out, int /*nthreads*/) {
+    if (!out || !conv_tab_ok(t) || !t->state || !t->alive) return RSK_EINVAL;
+    if (!t->cur_in || !t->cur_out || !t->prev_in || !t->prev_out) return RSK_EINVAL;
+    if (out->dead_rows && !out->n_dead) return RSK_EINVAL;
+    uint32_t n_dead = 0, n_alive = 0;
+    for (uint32_t r = 0; r < t->capacity; ++r) {
+        if (!(t->state[r] & RSK_CONN_LIVE)) continue;
+        if (!t->alive[r]) {  // IGroup::Flush closes it before the flush loop
+            if (out->dead_rows) out->dead_rows[n_dead] = r;
+            ++n_dead;
+            continue;
+        }
+        // DataStat::Flush (conn/IConn.cpp:70-79)
+        const bool alive = t->prev_in[r] != t->cur_in[r] && t->prev_out[r] != t->cur_out[r];
+        if (!alive) t->alive[r] = 0;
+        t->prev_in[r] = t->cur_in[r];
+        t->prev_out[r] = t->cur_out[r];
+        n_alive += alive;
+    }
+    if (out->n_dead) *out->n_dead = n_dead;
+    if (out->n_alive) *out->n_alive = n_alive;
     return RSK_OK;
 }
 

@@ -1,0 +1,742 @@
+"""TEST INFRASTRUCTURE: the conv table (rsk_conv_table, include/rsk_codec.h) restated with a dict and numpy,
+the scenarios the CPU and GPU tests share (side "cpu" = the host twins, a device = the kernels), and the
+driver that runs either side with every output pre-filled with a sentinel.
+
+The reference keeps the level per packet: SubGroup::OnRecv looks BuildConvKey(dst, conv) up in the SubGroup
+of the packet's IdBuf (server/SubGroup.cpp:31-50, server/ServerGroup.cpp:44-60), ClientGroup::OnRecv looks
+conv up in mConvMap and answers an unknown one with SendConvRst (client/ClientGroup.cpp:65-80); every conv
+counts its packets (IConn::DataStat, conn/IConn.cpp:63-79) and IGroup::Flush (conn/IGroup.cpp:81-107) closes
+the quiet ones."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from rsock_amd import _abi as A
+from tests import conn_ref as CR
+
+NONE = A.CONN_NONE
+NO_RST = 0xFFFFFFFF
+SENT = 0x6E  # the byte every output is filled with before a call
+MSG_COLS = ("cmd", "body", "id", "src", "avoid_key", "pay_off", "pay_len")
+COUNTERS = ("cur_in", "cur_out", "prev_in", "prev_out")
+FLAG_COMBOS = ((False, False), (True, False), (False, True), (True, True))  # (by_dst, by_id)
+GOLDEN_SERVER = ("server_small", "server_many_groups", "server_dense_ctrl", "server_tile_edges",
+                 "server_one_conv_many_conns", "server_one_packet", "server_all_dropped")
+GOLDEN_CLIENT_MSGS = {"client_small": 285, "client_large": 10517, "client_tile_edges": 0}
+SIZES = (1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097)
+CAPACITIES = (1, 2, 257, 65536)
+
+id_words = CR.id_words
+golden_case = CR.golden_case
+
+
+# ---- the restatement -----------------------------------------------------------------------------------
+def row_key(cols, r, by_dst, by_id, idw):
+    return (int(idw[r]) if by_id else 0, int(cols["dst"][r]) if by_dst else 0, int(cols["conv"][r]))
+
+
+def table_map(cols, by_dst, by_id):
+    """-> ({(id word, dst, conv): lowest LIVE row}, number of LIVE rows that lost their key)."""
+    cap = len(cols["state"])
+    idw = id_words(cols.get("id") if by_id else None, cap)
+    m, dup = {}, 0
+    for r in np.nonzero(cols["state"] & A.CONN_LIVE)[0].tolist():
+        k = row_key(cols, r, by_dst, by_id, idw)
+        if k in m:
+            dup += 1
+        else:
+            m[k] = r
+    return m, dup
+
+
+def examined(c):
+    ex = np.asarray(c["status"]) == A.RECV_VALID
+    if c.get("cmd") is not None:
+        ex &= np.asarray(c["cmd"]) == A.CMD_DATA
+    if c.get("hit") is not None:
+        ex &= np.asarray(c["hit"]) != 0
+    return ex
+
+
+def packet_keys(c, by_dst, by_id):
+    """Per packet (examined, is reset, key tuple or None)."""
+    n = len(c["status"])
+    ex = examined(c)
+    rst = np.zeros(n, bool)
+    if c.get("ctl_kind") is not None and by_dst:
+        rst = ~ex & (np.asarray(c["ctl_kind"]) == A.CTL_CONV_RST)
+    idw = id_words(c.get("id") if by_id else None, n)
+    keys = [None] * n
+    for i in np.nonzero(ex | rst)[0].tolist():
+        cv = int(c["conv"][i]) if ex[i] else int(c["ctl_arg"][i]) & 0xFFFFFFFF
+        keys[i] = (int(idw[i]) if by_id else 0, int(c["dst"][i]) if by_dst else 0, cv)
+    return ex, rst, keys
+
+
+def resolve_ref(cols, by_dst, by_id, c):
+    """rsk_conv_resolve_batch on the table as indexed: -> dict(conv_row, unknown, n_unknown, rst_first,
+    add = the packets per row that count into cur_in, msgs = dict of the message columns)."""
+    cap, n = len(cols["state"]), len(c["status"])
+    tmap, _ = table_map(cols, by_dst, by_id)
+    ex, rst, keys = packet_keys(c, by_dst, by_id)
+    row = np.full(n, NONE, np.uint32)
+    for i in np.nonzero(ex | rst)[0].tolist():
+        row[i] = tmap.get(keys[i], NONE)
+    unk = ex & (row == NONE)
+    rst_first = np.full(cap, NO_RST, np.uint32)
+    hit_rst = np.nonzero(rst & (row != NONE))[0]
+    np.minimum.at(rst_first, row[hit_rst].astype(np.int64), hit_rst.astype(np.uint32))
+    add = np.bincount(row[ex & (row != NONE)].astype(np.int64), minlength=cap).astype(np.uint32)
+    u = np.nonzero(unk)[0]
+    ids = np.zeros((len(u), 8), np.uint8) if c.get("id") is None else np.asarray(c["id"], np.uint8).reshape(n, 8)[u]
+    msgs = {"cmd": np.full(len(u), A.CMD_CONV_RST, np.uint8), "body": np.asarray(c["conv"])[u].astype(np.uint64),
+            "id": ids, "src": u.astype(np.uint32), "avoid_key": np.zeros(len(u), np.uint64),
+            "pay_off": 8 * np.arange(len(u), dtype=np.uint64), "pay_len": np.full(len(u), 4, np.uint16)}
+    return {"conv_row": row, "unknown": np.where(unk, A.RECV_VALID, A.RECV_DROP).astype(np.int8), "n_unknown": len(u),
+            "rst_first": rst_first, "add": add, "msgs": msgs}
+
+
+def sequential_ref(cols, by_dst, by_id, c):
+    """The reference's per-packet walk: a CONV_RST that hits closes its conv (OnRecvConvRst -> CloseConn),
+    so later packets see the key gone.  -> conv_row per packet."""
+    tmap, _ = table_map(cols, by_dst, by_id)
+    ex, rst, keys = packet_keys(c, by_dst, by_id)
+    row = np.full(len(keys), NONE, np.uint32)
+    for i, k in enumerate(keys):
+        if k is None:
+            continue
+        row[i] = tmap.get(k, NONE)
+        if rst[i] and k in tmap:
+            del tmap[k]
+    return row
+
+
+def send_ref(cols, conv_row, sent=None):
+    """rsk_conv_send_batch: -> (dict conv, dst, id [n*8], ok; n_bad; the adds to cur_out per row)."""
+    cap = len(cols["state"])
+    conv_row = np.asarray(conv_row, np.uint32)
+    inside = conv_row < cap
+    r = np.where(inside, conv_row, 0).astype(np.int64)
+    ok = inside & ((cols["state"][r] & A.CONN_LIVE) != 0)
+    out = {"conv": np.where(ok, cols["conv"][r], 0).astype(np.uint32), "ok": ok.astype(np.uint8)}
+    if cols.get("dst") is not None:
+        out["dst"] = np.where(ok, cols["dst"][r], 0).astype(np.uint32)
+    if cols.get("id") is not None:
+        out["id"] = np.where(ok, id_words(cols["id"], cap)[r], 0).astype(np.uint64).view(np.uint8)
+    cnt = ok if sent is None else ok & (np.asarray(sent) > 0)
+    add = np.bincount(r[cnt], minlength=cap).astype(np.uint32) if sent is not None else np.zeros(cap, np.uint32)
+    return out, int((~ok).sum()), add
+
+
+def flush_ref(cols):
+    """rsk_conv_flush on copies of the columns: -> (new columns, dead_rows, n_alive)."""
+    o = {k: cols[k].copy() for k in ("alive",) + COUNTERS}
+    live = (cols["state"] & A.CONN_LIVE) != 0
+    dead = np.nonzero(live & (cols["alive"] == 0))[0].astype(np.uint32)
+    fl = live & (cols["alive"] != 0)
+    alive = fl & (cols["prev_in"] != cols["cur_in"]) & (cols["prev_out"] != cols["cur_out"])
+    o["alive"][fl] = alive[fl]
+    o["prev_in"][fl] = cols["cur_in"][fl]
+    o["prev_out"][fl] = cols["cur_out"][fl]
+    return o, dead, int(alive.sum())
+
+
+# ---- tables and batches ----------------------------------------------------------------------------------
+def random_columns(rng, capacity, by_dst=True, by_id=True):
+    """Columns with random keys and counters, every row alive, no LIVE row (numpy, unsigned dtypes)."""
+    r32 = lambda: rng.integers(0, 2**32, capacity, dtype=np.uint64).astype(np.uint32)  # noqa: E731
+    cols = {"state": np.zeros(capacity, np.uint8), "conv": r32(), "dst": r32() if by_dst else None,
+            "id": rng.integers(0, 256, capacity * 8, dtype=np.uint64).astype(np.uint8) if by_id else None,
+            "cur_in": r32(), "cur_out": r32(), "prev_in": r32(), "prev_out": r32(), "alive": np.ones(capacity, np.uint8)}
+    return cols
+
+
+def make_table(rc, cols, device, by_dst, by_id, codec=None, counters=True):
+    """A rsock_amd.codec.ConvTable on `device` holding `cols`, index built there."""
+    tab = rc.ConvTable.alloc(len(cols["state"]), device, by_dst=by_dst, by_id=by_id)
+    tab.load(**{k: v for k, v in cols.items() if v is not None})
+    if not counters:
+        tab.cur_in = None
+    tab.rebuild(codec)
+    return tab
+
+
+def random_case(rng, n, capacity, by_dst, by_id, known=0.8, live=0.8, pool=None, ctl=True, hit=True):
+    """A table whose keys come from a small pool of values that differ in single bits of conv / dst / IdBuf
+    (with duplicate keys among the rows) and a batch of DATA packets for known and unknown keys, control
+    packets (CONV_RST with its ctl pair) and dropped ones: -> (cols, c)."""
+    cols = random_columns(rng, capacity, by_dst, by_id)
+    pool = min(capacity, pool or capacity)
+    base_c = rng.integers(0, 2**32, dtype=np.uint64)
+    pc = (base_c ^ rng.integers(0, 2**32, pool, dtype=np.uint64) * (rng.random(pool) < 0.7)).astype(np.uint32)
+    pc[: min(pool, 33)] = (base_c ^ (np.uint64(1) << np.arange(min(pool, 33), dtype=np.uint64) % 32)).astype(np.uint32)
+    pd = rng.choice(np.array([0x0A000001, 0x0A000001 ^ 0x80000000, 0x0A000003, 0, 0xFFFFFFFF], np.uint32), pool)
+    ids = np.array([[1, 2, 3, 4, 5, 6, 7, 8], [1, 2, 3, 4, 5, 6, 7, 9], [0] * 8, [255] * 8, [129, 2, 3, 4, 5, 6, 7, 8]], np.uint8)
+    pi = rng.integers(0, len(ids), pool)
+    rows = rng.permutation(capacity)
+    slot = np.arange(capacity) % pool  # row rows[j] holds pool key slot[j]: duplicates once capacity > pool
+    cols["conv"][rows] = pc[slot]
+    if by_dst:
+        cols["dst"][rows] = pd[slot]
+    if by_id:
+        cols["id"].reshape(-1, 8)[rows] = ids[pi[slot]]
+    cols["state"][:] = np.where(rng.random(capacity) < live, A.CONN_LIVE, 0) | (rng.integers(0, 2, capacity) << 1)
+    j = rng.integers(0, pool, n)
+    conv, dst, idb = pc[j].copy(), pd[j].copy(), ids[pi[j]].copy()
+    unk = rng.random(n) > known  # one bit off in one of the key's parts
+    which = rng.integers(0, 3, n)
+    conv[unk & (which == 0)] ^= np.uint32(1) << rng.integers(0, 32, n, dtype=np.uint32)[unk & (which == 0)]
+    dst[unk & (which == 1)] ^= np.uint32(0x00010000)
+    idb[unk & (which == 2), 5] ^= 0x40
+    status = rng.choice(np.array([1, 1, 1, 1, 1, 1, 1, 1, 0, -1], np.int8), n)
+    cmd = rng.choice(np.array([0, 0, 0, 0, 0, 0, 0, 1, 1, 2, 3, 4, 9], np.uint8), n)
+    c = {"status": status, "cmd": cmd, "conv": conv, "dst": dst if by_dst else None, "id": idb.ravel() if by_id else None,
+         "hit": (rng.random(n) < 0.9).astype(np.uint8) if hit else None, "ctl_kind": None, "ctl_arg": None}
+    if ctl:
+        is_rst = (status == A.RECV_VALID) & (cmd == A.CMD_CONV_RST)
+        kind = np.where(status == A.RECV_VALID, np.minimum(cmd, A.CTL_UNKNOWN), A.CTL_NONE).astype(np.uint8)
+        kind[is_rst & (rng.random(n) < 0.1)] = A.CTL_SHORT
+        # the body's conv: the key of the pool entry (the packet's own conv field is something else), with
+        # bits above the low 32 that the lookup must drop
+        c["ctl_arg"] = np.where(is_rst, pc[j].astype(np.uint64) | (rng.integers(0, 2, n, dtype=np.uint64) << 40),
+                                rng.integers(0, 2**63, n, dtype=np.uint64))
+        c["conv"] = np.where(is_rst, rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32), conv)
+        c["ctl_kind"] = kind
+    return cols, c
+
+
+def tensor(a, device):
+    """A numpy array as a torch tensor of the signed dtype of its width on `device` (None stays None)."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(np.uint8 if a.dtype == np.uint8 else f"i{a.dtype.itemsize}").copy()).to(device)
+
+
+def host(t, dt):
+    return t.cpu().numpy().view(dt)
+
+
+def filled(n, dt, device):
+    t = torch.empty(max(n, 1), dtype=dt, device=device)
+    t.view(torch.uint8).fill_(SENT)
+    return t
+
+
+# ---- the driver --------------------------------------------------------------------------------------------
+OUTPUTS = ("unknown", "n_unknown", "rst_first")
+MSG_MODES = ("all", "none", "count", "body")
+
+
+def run_resolve(rc, tab, c, device, codec=None, want=OUTPUTS, msg_mode="all", slack=3, stream=None, nthreads=1):
+    """One resolve on `device` ("cpu": the host twin) with every output pre-filled with SENT and `slack`
+    spare entries behind each: -> dict of numpy outputs incl. msgs (the first n_msg entries) and "tail_ok"
+    (nothing behind the entries a call may write was touched)."""
+    n = len(c["status"])
+    t = {k: tensor(v, device) for k, v in c.items()}
+    o = {"conv_row": filled(n + slack, torch.int32, device),
+         "unknown": filled(n + slack, torch.int8, device) if "unknown" in want else None,
+         "n_unknown": filled(1, torch.int32, device) if "n_unknown" in want else None,
+         "rst_first": filled(tab.capacity + slack, torch.int32, device) if "rst_first" in want else None}
+    msgs = None
+    if msg_mode != "none":
+        msgs = rc.ControlBuffers.alloc(n + slack, device)
+        for f in ("msg_cmd", "msg_body", "msg_id", "msg_src", "msg_avoid_key", "msg_pay_off", "msg_pay_len", "n_msg"):
+            getattr(msgs, f).view(torch.uint8).fill_(SENT)
+            if (msg_mode == "count" and f != "n_msg") or (msg_mode == "body" and f not in ("msg_body", "n_msg")):
+                setattr(msgs, f, None)
+    kw = dict(cmd=t["cmd"], hit=t["hit"], id=t["id"], dst=t["dst"], ctl_kind=t["ctl_kind"], ctl_arg=t["ctl_arg"],
+              unknown=o["unknown"], n_unknown=o["n_unknown"], rst_first=o["rst_first"], msgs=msgs)
+    if codec is None:
+        rc.conv_resolve_host(tab, t["status"], t["conv"], o["conv_row"], nthreads=nthreads, **kw)
+    else:
+        codec.conv_resolve_batch(tab, t["status"], t["conv"], o["conv_row"], stream=stream, **kw)
+        torch.cuda.synchronize()
+    sent32 = int.from_bytes(bytes([SENT] * 4), "little")
+    got = {"conv_row": host(o["conv_row"], np.uint32)[:n], "tail_ok": bool((host(o["conv_row"], np.uint32)[n:] == sent32).all())}
+    if o["unknown"] is not None:
+        got["unknown"] = host(o["unknown"], np.int8)[:n]
+        got["tail_ok"] &= bool((host(o["unknown"], np.uint8)[n:] == SENT).all())
+    if o["n_unknown"] is not None:
+        got["n_unknown"] = int(host(o["n_unknown"], np.uint32)[0])
+    if o["rst_first"] is not None:
+        got["rst_first"] = host(o["rst_first"], np.uint32)[:tab.capacity]
+        got["tail_ok"] &= bool((host(o["rst_first"], np.uint32)[tab.capacity:] == sent32).all())
+    if msgs is not None:
+        got["n_msg"] = k = int(host(msgs.n_msg, np.uint32)[0])
+        got["msgs"] = msgs.messages()
+        for f, w in (("msg_cmd", 1), ("msg_body", 1), ("msg_id", 8), ("msg_src", 1), ("msg_pay_len", 1)):
+            col = getattr(msgs, f)
+            if col is not None:
+                got["tail_ok"] &= bool((col[k * w:].cpu().view(torch.uint8).numpy() == SENT).all())
+    return got
+
+
+def compare(got, want):
+    assert got["tail_ok"]
+    assert np.array_equal(got["conv_row"], want["conv_row"]), "conv_row"
+    if "unknown" in got:
+        assert np.array_equal(got["unknown"], want["unknown"]), "unknown"
+    if "n_unknown" in got:
+        assert got["n_unknown"] == want["n_unknown"]
+    if "rst_first" in got:
+        assert np.array_equal(got["rst_first"], want["rst_first"]), "rst_first"
+    if "msgs" in got:
+        assert got["n_msg"] == want["n_unknown"]
+        for k, v in got["msgs"].items():
+            assert np.array_equal(v, want["msgs"][k]), k
+
+
+def check_case(rc, cols, c, by_dst, by_id, device, codec=None, counters=True, **kw):
+    """Table from `cols`, one resolve of `c`, everything against resolve_ref; cur_in advanced exactly (mod
+    2^32) and no other counter column touched: -> (got, want, tab)."""
+    tab = make_table(rc, cols, device, by_dst, by_id, codec, counters=counters)
+    want = resolve_ref(cols, by_dst, by_id, c)
+    got = run_resolve(rc, tab, c, device, codec, **kw)
+    compare(got, want)
+    if counters:
+        assert np.array_equal(tab.column("cur_in"), cols["cur_in"] + want["add"]), "cur_in"
+    for k in ("cur_out", "prev_in", "prev_out", "alive", "state", "conv"):
+        assert np.array_equal(tab.column(k), cols[k]), k
+    return got, want, tab
+
+
+# ---- shared scenarios ---------------------------------------------------------------------------------------
+def golden_client(name, capacity=97, seed=5):
+    """Client case `name`: hit from its known_keys, and a conv table with its known_convs at shuffled rows
+    of a larger capacity whose spare rows hold convs of the batch but are not LIVE."""
+    g = golden_case(name)
+    rng = np.random.default_rng(seed)
+    cols = random_columns(rng, capacity, False, False)
+    kc = g["known_convs"]
+    rows = rng.permutation(capacity)[:len(kc)]
+    cols["conv"][:] = rng.choice(np.unique(g["conv"]), capacity)
+    cols["conv"][rows] = kc
+    cols["state"][rows] = A.CONN_LIVE
+    c = {"status": g["status"], "cmd": g["cmd"], "conv": g["conv"], "id": g["id"], "dst": None,
+         "hit": np.isin(g["conn_key"], g["known_keys"]).astype(np.uint8), "ctl_kind": None, "ctl_arg": None}
+    return g, cols, c
+
+
+def scenario_golden_client(rc, name, device, codec=None):
+    g, cols, c = golden_client(name)
+    got, want, _tab = check_case(rc, cols, c, False, False, device, codec)
+    leaf, row = g["leaf"], got["conv_row"]
+    assert np.array_equal(row != NONE, leaf >= 0)
+    on = leaf >= 0
+    pairs = np.unique(np.stack([row[on].astype(np.int64), leaf[on].astype(np.int64)], axis=1), axis=0)
+    assert len(pairs) == len(np.unique(pairs[:, 0])) == len(np.unique(pairs[:, 1]))  # share a row <=> share a leaf
+    assert np.array_equal(got["unknown"] == A.RECV_VALID, g["rst_conv"] >= 0)
+    assert np.array_equal(got["msgs"]["body"], g["rst_conv"][g["rst_conv"] >= 0].astype(np.uint64))
+    assert got["n_msg"] == GOLDEN_CLIENT_MSGS[name]
+    # cur_in per row = the reference's packets per leaf
+    per_leaf = np.bincount(leaf[on])
+    for r, lf in pairs.tolist():
+        assert want["add"][r] == per_leaf[lf]
+
+
+def first_arrivals(c, unknown, by_dst=True, by_id=True):
+    """Packet indices of the first packet of each distinct key among the unknown ones, in arrival order."""
+    _ex, _rst, keys = packet_keys(c, by_dst, by_id)
+    seen, out = set(), []
+    for i in np.nonzero(np.asarray(unknown) == A.RECV_VALID)[0].tolist():
+        if keys[i] not in seen:
+            seen.add(keys[i])
+            out.append(i)
+    return np.array(out, np.int64)
+
+
+def scenario_golden_server(rc, name, device, codec=None, first_fn=None):
+    """Phase 1: an empty table marks every VALID DATA packet unknown; the distinct keys in first-arrival
+    order (first_fn(c, unknown) on the GPU side: rsk_demux_batch's seg_first) become rows 0, 1, ...
+    Phase 2: conv_row == the reference's leaf, cur_in == bincount(leaf)."""
+    g = golden_case(name)
+    c = {"status": g["status"], "cmd": g["cmd"], "conv": g["conv"], "id": g["id"], "dst": g["dst"], "hit": None,
+         "ctl_kind": None, "ctl_arg": None}
+    n = len(g["status"])
+    data = (g["status"] == A.RECV_VALID) & (g["cmd"] == A.CMD_DATA)
+    cap = max(1, len(np.unique(g["leaf"][g["leaf"] >= 0])) + 5)
+    cols = random_columns(np.random.default_rng(1), cap)
+    cols["cur_in"][:] = 0
+    got, _want, _tab = check_case(rc, cols, c, True, True, device, codec, msg_mode="count")
+    assert np.array_equal(got["unknown"] == A.RECV_VALID, data) and got["n_unknown"] == int(data.sum())
+    first = first_arrivals(c, got["unknown"])
+    if first_fn is not None:
+        assert np.array_equal(first_fn(c, got["unknown"]), first)
+    k = len(first)
+    cols["conv"][:k], cols["dst"][:k] = g["conv"][first], g["dst"][first]
+    cols["id"].reshape(-1, 8)[:k] = g["id"].reshape(n, 8)[first]
+    cols["state"][:k] = A.CONN_LIVE
+    got, _want, tab = check_case(rc, cols, c, True, True, device, codec)
+    assert np.array_equal(got["conv_row"].view(np.int32), g["leaf"]) and got["n_unknown"] == 0
+    assert np.array_equal(tab.column("cur_in"), np.bincount(g["leaf"][g["leaf"] >= 0], minlength=cap).astype(np.uint32))
+
+
+def scenario_sizes(rc, n, capacity, device, codec=None, by_dst=True, by_id=True):
+    rng = np.random.default_rng(1000 * n + capacity + 7 * by_dst + 13 * by_id)
+    cols, c = random_case(rng, n, capacity, by_dst, by_id, pool=min(capacity, 300))
+    got, want, _ = check_case(rc, cols, c, by_dst, by_id, device, codec, nthreads=3)
+    return got, want
+
+
+def scenario_skew(rc, kind, device, codec=None):
+    """Exact counts under skew, from counters preset just below the wrap."""
+    rng = np.random.default_rng(23)
+    if kind == "one_row":
+        n, cap = 70000, 300
+        rows = np.full(n, 117)
+    elif kind == "all_rows":
+        n = cap = 65536
+        rows = rng.permutation(cap)
+    elif kind == "alternate":
+        n, cap = 9000, 64
+        rows = np.where(np.arange(n) % 2 == 0, 5, 40)
+    else:  # runs: bursts of neighbours on one conv, the length of a run no multiple of the wave
+        n, cap = 30000, 1000
+        rows = np.repeat(rng.integers(0, cap, n // 37 + 1), 37)[:n]
+    cols = random_columns(rng, cap, False, False)
+    cols["conv"][:] = rng.permutation(np.arange(cap, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(9))
+    cols["state"][:] = A.CONN_LIVE
+    cols["cur_in"][:] = 0xFFFFFFF0
+    c = {"status": np.ones(n, np.int8), "cmd": None, "conv": cols["conv"][rows], "id": None, "dst": None, "hit": None,
+         "ctl_kind": None, "ctl_arg": None}
+    got, want, tab = check_case(rc, cols, c, False, False, device, codec, msg_mode="none", nthreads=4)
+    assert np.array_equal(got["conv_row"], rows.astype(np.uint32))
+    cur = tab.column("cur_in")
+    assert np.array_equal(cur, (0xFFFFFFF0 + np.bincount(rows, minlength=cap)).astype(np.uint64).astype(np.uint32))
+    if kind in ("one_row", "alternate"):  # more than 16 packets on a row: the wrap happened
+        assert int(cur.min()) < 0xFFFFFFF0
+
+
+def scenario_conv_rst(rc, device, codec=None):
+    rng = np.random.default_rng(31)
+    for by_id in (False, True):
+        cols, c = random_case(rng, 6000, 40, True, by_id, known=0.9, live=0.9, pool=12)
+        rstp = (c["ctl_kind"] == A.CTL_CONV_RST) & (c["status"] == A.RECV_VALID)
+        assert rstp.sum() > 200
+        got, want, _ = check_case(rc, cols, c, True, by_id, device, codec)
+        hit_rows = np.nonzero(want["rst_first"] != NO_RST)[0]
+        assert len(hit_rows) >= 5 and bool((got["conv_row"][rstp] != NONE).any()) and bool((got["conv_row"][rstp] == NONE).any())
+        # snapshot rule: a packet at or before its row's rst_first gets what the per-packet walk gives it
+        seq = sequential_ref(cols, True, by_id, c)
+        snap = got["conv_row"]
+        assert bool((seq[snap == NONE] == NONE).all())
+        i = np.nonzero(snap != NONE)[0]
+        upto = i <= want["rst_first"][snap[i].astype(np.int64)]
+        assert np.array_equal(seq[i[upto]], snap[i[upto]]) and bool((seq[i[~upto]] == NONE).all()) and (~upto).sum() > 0
+    # a client table never hits a CONV_RST, whatever its body holds
+    cols, c = random_case(rng, 3000, 40, False, False, pool=12)
+    got, want, _ = check_case(rc, cols, c, False, False, device, codec)
+    rstp = c["ctl_kind"] == A.CTL_CONV_RST
+    assert rstp.sum() > 100 and bool((got["conv_row"][rstp & ~examined(c)] == NONE).all())
+    assert bool((got["rst_first"] == NO_RST).all())
+
+
+def scenario_reads(rc, device, codec=None):
+    """Packets that are not looked up carry poisoned key fields; no output depends on them."""
+    rng = np.random.default_rng(41)
+    cols, c = random_case(rng, 5000, 300, True, True, pool=50)
+    ex, rst, _ = packet_keys(c, True, True)
+    skip = ~(ex | rst)
+    assert skip.sum() > 500
+    outs = []
+    for poison in (0x00, 0xFF, 0x5A):
+        p = dict(c)
+        for k, w in (("conv", 1), ("dst", 1), ("ctl_arg", 1)):
+            a = c[k].copy()
+            if k == "conv":
+                a[skip] = a.dtype.type(int.from_bytes(bytes([poison] * a.dtype.itemsize), "little"))
+            else:
+                a[skip if k == "dst" else ~rst] = a.dtype.type(int.from_bytes(bytes([poison] * a.dtype.itemsize), "little"))
+            p[k] = a
+        idb = c["id"].reshape(-1, 8).copy()
+        idb[skip] = poison
+        p["id"] = idb.ravel()
+        got, _, tab = check_case(rc, cols, p, True, True, device, codec, msg_mode="body")
+        outs.append((got, tab.column("cur_in")))
+    for got, cur in outs[1:]:
+        for k in ("conv_row", "unknown", "rst_first"):
+            assert np.array_equal(got[k], outs[0][0][k])
+        assert np.array_equal(cur, outs[0][1]) and got["n_msg"] == outs[0][0]["n_msg"]
+
+
+def scenario_optional_outputs(rc, device, codec=None):
+    rng = np.random.default_rng(43)
+    cols, c = random_case(rng, 4500, 200, True, True, pool=60)
+    for want in (OUTPUTS, (), ("unknown",), ("n_unknown",), ("rst_first",)):
+        for mode in MSG_MODES:
+            check_case(rc, cols, c, True, True, device, codec, want=want, msg_mode=mode)
+    check_case(rc, cols, c, True, True, device, codec, counters=False)
+    for k in ("cmd", "hit", "ctl"):
+        p = dict(c)
+        if k == "ctl":
+            p["ctl_kind"] = p["ctl_arg"] = None
+        else:
+            p[k] = None
+        check_case(rc, cols, p, True, True, device, codec)
+    p = dict(c, id=None)  # a table without BY_ID: messages carry zeros for the IdBuf
+    check_case(rc, {**cols, "id": None}, p, True, False, device, codec)
+
+
+def run_send(rc, tab, conv_row, device, codec=None, sent=None, cols=("conv", "dst", "id", "ok", "n_bad")):
+    n = len(conv_row)
+    o = {"conv": filled(n + 2, torch.int32, device), "dst": filled(n + 2, torch.int32, device) if tab.by_dst else None,
+         "id": filled(8 * (n + 2), torch.uint8, device) if tab.by_id else None, "ok": filled(n + 2, torch.uint8, device),
+         "n_bad": filled(1, torch.int32, device)}
+    o = {k: (v if k in cols else None) for k, v in o.items()}
+    args = (tab, tensor(np.asarray(conv_row, np.uint32), device))
+    kw = dict(sent=tensor(sent, device), **o)
+    if codec is None:
+        rc.conv_send_host(*args, **kw)
+    else:
+        codec.conv_send_batch(*args, **kw)
+        torch.cuda.synchronize()
+    got = {}
+    for k, dt, w in (("conv", np.uint32, 1), ("dst", np.uint32, 1), ("id", np.uint8, 8), ("ok", np.uint8, 1)):
+        if o[k] is not None:
+            a = host(o[k], dt)
+            got[k] = a[:n * w]
+            assert bool((a[n * w:].view(np.uint8) == SENT).all()), k
+    if o["n_bad"] is not None:
+        got["n_bad"] = int(host(o["n_bad"], np.uint32)[0])
+    return got
+
+
+def scenario_send(rc, device, codec=None, n=5000):
+    rng = np.random.default_rng(47)
+    cap = 100
+    for by_dst, by_id in FLAG_COMBOS:
+        cols = random_columns(rng, cap, by_dst, by_id)
+        cols["state"][:] = rng.choice(np.array([0, A.CONN_LIVE, 2, 3, 0x81], np.uint8), cap)
+        cols["state"][3] = A.CONN_LIVE
+        cols["cur_out"][:5] = 0xFFFFFFFF
+        conv_row = rng.integers(0, cap, n).astype(np.uint32)
+        conv_row[n // 2: n // 2 + 700] = 3  # a burst on one row
+        odd = rng.random(n) < 0.1
+        conv_row[odd] = rng.choice(np.array([NONE, cap, cap + 1, 2**31], np.uint32), int(odd.sum()))
+        sent = rng.choice(np.array([-1, 0, 32, 1500], np.int32), n)
+        tab = make_table(rc, cols, device, by_dst, by_id, codec)
+        # the two-call form: expand before the encode, count after it
+        want, n_bad, add = send_ref(cols, conv_row, sent)
+        got = run_send(rc, tab, conv_row, device, codec)
+        assert got.pop("n_bad") == n_bad and 0 < n_bad < n
+        for k, v in want.items():
+            assert np.array_equal(got[k], v), k
+        assert np.array_equal(tab.column("cur_out"), cols["cur_out"])  # no counting without `sent`
+        got = run_send(rc, tab, conv_row, device, codec, sent=sent, cols=("n_bad",))
+        assert got == {"n_bad": n_bad}
+        assert np.array_equal(tab.column("cur_out"), cols["cur_out"] + add) and add.sum() > 0
+        assert int(add[3]) >= 150 and np.array_equal(tab.column("cur_in"), cols["cur_in"])
+        # one call doing both
+        got = run_send(rc, tab, conv_row, device, codec, sent=sent)
+        assert np.array_equal(got["ok"], want["ok"]) and np.array_equal(tab.column("cur_out"), cols["cur_out"] + add + add)
+
+
+def run_flush(rc, tab, device, codec=None, want=("dead_rows", "n_dead", "n_alive")):
+    o = {"dead_rows": filled(tab.capacity + 2, torch.int32, device) if "dead_rows" in want else None,
+         "n_dead": filled(1, torch.int32, device) if "n_dead" in want else None,
+         "n_alive": filled(1, torch.int32, device) if "n_alive" in want else None}
+    if codec is None:
+        rc.conv_flush_host(tab, **o)
+    else:
+        codec.conv_flush(tab, **o)
+        torch.cuda.synchronize()
+    got = {k: int(host(o[k], np.uint32)[0]) for k in ("n_dead", "n_alive") if o[k] is not None}
+    if o["dead_rows"] is not None:
+        a = host(o["dead_rows"], np.uint32)
+        got["dead_rows"] = a[:got["n_dead"]]
+        assert bool((a[got["n_dead"]:].view(np.uint8) == SENT).all())
+    return got
+
+
+def scenario_flush_steps(rc, capacity, device, codec=None):
+    rng = np.random.default_rng(capacity)
+    cols = random_columns(rng, capacity, False, False)
+    cols["state"][:] = rng.choice(np.array([0, A.CONN_LIVE, 2, 3], np.uint8), capacity)
+    cols["alive"][:] = rng.choice(np.array([0, 1, 1, 1], np.uint8), capacity)
+    same_in, same_out = rng.random(capacity) < 0.3, rng.random(capacity) < 0.3
+    cols["prev_in"][same_in] = cols["cur_in"][same_in]
+    cols["prev_out"][same_out] = cols["cur_out"][same_out]
+    tab = make_table(rc, cols, device, False, False, codec)
+    for want in (("dead_rows", "n_dead", "n_alive"), ("n_alive",), ("n_dead",), ()):
+        new, dead, n_alive = flush_ref(cols)
+        got = run_flush(rc, tab, device, codec, want=want)
+        if "dead_rows" in want:
+            assert np.array_equal(got["dead_rows"], dead)
+        assert got.get("n_dead", len(dead)) == len(dead) and got.get("n_alive", n_alive) == n_alive
+        for k, v in new.items():
+            assert np.array_equal(tab.column(k), v), k
+        assert np.array_equal(tab.column("cur_in"), cols["cur_in"]) and np.array_equal(tab.column("state"), cols["state"])
+        cols.update(new)  # the next pass starts from this one's columns: marked rows are listed now
+
+
+def scenario_flush_life(rc, device, codec=None):
+    """Rows 0..3 LIVE: 0 has traffic both ways, 1 only in, 2 only out, 3 none; row 4 is not LIVE."""
+    rng = np.random.default_rng(3)
+    cols = random_columns(rng, 6, False, False)
+    cols["conv"][:] = np.arange(10, 16)
+    cols["state"][:4] = A.CONN_LIVE
+    for k in COUNTERS:
+        cols[k][:] = 0
+    cols["cur_in"][3] = cols["prev_in"][3] = 0xFFFFFFFF
+    tab = make_table(rc, cols, device, False, False, codec)
+    c = {"status": np.ones(5, np.int8), "cmd": None, "conv": np.array([10, 11, 10, 14, 99], np.uint32), "id": None,
+         "dst": None, "hit": None, "ctl_kind": None, "ctl_arg": None}
+    for rnd, (alive, dead) in enumerate([([1, 0, 0, 0], []), ([1, 0, 0, 0], [1, 2, 3]), ([1, 0, 0, 0], [1, 2, 3])]):
+        got = run_resolve(rc, tab, c, device, codec)
+        assert got["conv_row"].tolist() == [0, 1, 0, NONE, NONE] and got["n_unknown"] == 2
+        run_send(rc, tab, np.array([0, 2, 4, 9], np.uint32), device, codec, sent=np.array([40, 40, 40, 40], np.int32), cols=())
+        before = {k: tab.column(k) for k in COUNTERS}
+        got = run_flush(rc, tab, device, codec)
+        assert got["dead_rows"].tolist() == dead and got["n_alive"] == 1, rnd  # written, not accumulated
+        assert tab.column("alive")[:4].tolist() == alive and tab.column("alive")[4] == 1
+        assert tab.column("cur_in").tolist() == [2 * (rnd + 1), rnd + 1, 0, 0xFFFFFFFF, 0, 0]
+        assert tab.column("cur_out").tolist() == [rnd + 1, 0, rnd + 1, 0, 0, 0]
+        if dead:  # a not-alive row's counters are left alone: prev does not follow cur
+            for k in ("prev_in", "prev_out"):
+                assert np.array_equal(tab.column(k)[1:4], before[k][1:4])
+            assert tab.column("prev_in")[1] == 1 and tab.column("cur_in")[1] == rnd + 1
+        assert tab.column("prev_in")[0] == 2 * (rnd + 1)
+
+
+# ---- arguments ----------------------------------------------------------------------------------------------
+def einval_fixture(rc, device, codec=None):
+    rng = np.random.default_rng(2)
+    cols = random_columns(rng, 4)
+    cols["state"][1] = A.CONN_LIVE
+    tabs = {f: make_table(rc, {**cols, "dst": cols["dst"] if f[0] else None, "id": cols["id"] if f[1] else None},
+                          device, f[0], f[1], codec) for f in FLAG_COMBOS}
+    n = 3
+    a = {"status": tensor(np.ones(n, np.int8), device), "conv": tensor(np.full(n, 9, np.uint32), device),
+         "dst": tensor(np.zeros(n, np.uint32), device), "id": tensor(np.zeros(8 * n + 8, np.uint8), device),
+         "kind": tensor(np.zeros(n, np.uint8), device), "arg": tensor(np.zeros(n, np.uint64), device),
+         "row": filled(n, torch.int32, device), "cnt": filled(1, torch.int32, device), "body": filled(n, torch.int64, device),
+         "mid": filled(8 * n + 8, torch.uint8, device), "ok": filled(n, torch.uint8, device),
+         "sent": tensor(np.ones(n, np.int32), device), "dead": filled(4, torch.int32, device)}
+    return tabs, a, n
+
+
+def resolve_einval_cases(tabs, a, n):
+    """(label, table struct, n, in struct, out struct) of every RSK_EINVAL of the resolve; and the valid call."""
+    p = lambda k: a[k].data_ptr()  # noqa: E731
+
+    def rin(**kw):
+        d = dict(status=p("status"), cmd=None, hit=None, id=p("id"), conv=p("conv"), dst=p("dst"), ctl_kind=p("kind"),
+                 ctl_arg=p("arg"))
+        d.update(kw)
+        return A.ConvResolveIn(*[d[f] for f, _ in A.ConvResolveIn._fields_])
+
+    def rout(msgs=None, **kw):
+        d = dict(conv_row=p("row"), unknown=None, n_unknown=p("cnt"), rst_first=None)
+        d.update(kw)
+        return A.ConvResolveOut(d["conv_row"], d["unknown"], d["n_unknown"], d["rst_first"], msgs or A.CtlMsgs())
+
+    server, client = tabs[(True, True)], tabs[(False, False)]
+    cases = [("valid", t.abi(), n, rin(), rout(), A.OK) for t in tabs.values()]
+    cases.append(("valid-msgs", server.abi(), n, rin(), rout(A.CtlMsgs(body=p("body"), id=p("mid"), n_msg=p("cnt"))), A.OK))
+    E = A.EINVAL
+    cases += [("null tab", None, n, rin(), rout(), E), ("null in", server.abi(), n, None, rout(), E),
+              ("null out", server.abi(), n, rin(), None, E)]
+    for field, val in (("flags", 4), ("flags", 0x80000003), ("capacity", 0), ("capacity", A.CONN_MAX_ROWS + 1),
+                       ("state", None), ("conv", None), ("index", None), ("dst", None), ("id", None)):
+        t = server.abi()
+        setattr(t, field, val)
+        cases.append((f"tab.{field}={val}", t, n, rin(), rout(), E))
+    for field in ("status", "conv", "dst", "id"):
+        cases.append((f"in.{field}", server.abi(), n, rin(**{field: None}), rout(), E))
+    cases += [("client without dst/id", client.abi(), n, rin(dst=None, id=None), rout(), A.OK),
+              ("conv_row", server.abi(), n, rin(), rout(conv_row=None), E),
+              ("in.id misaligned", server.abi(), n, rin(id=p("id") + 4), rout(), E),
+              ("in.id misaligned, client", client.abi(), n, rin(id=p("id") + 4), rout(), E),
+              ("msgs.id misaligned", server.abi(), n, rin(), rout(A.CtlMsgs(id=p("mid") + 4, n_msg=p("cnt"))), E),
+              ("ctl half: kind", server.abi(), n, rin(ctl_arg=None), rout(), E),
+              ("ctl half: arg", server.abi(), n, rin(ctl_kind=None), rout(), E),
+              ("msgs without n_msg", server.abi(), n, rin(), rout(A.CtlMsgs(body=p("body"))), E),
+              ("n too large", server.abi(), A.MAX_BATCH + 1, rin(), rout(), E)]
+    t = server.abi()
+    t.id += 4
+    cases.append(("tab.id misaligned", t, n, rin(), rout(), E))
+    return cases
+
+
+def check_einval(rc, device, codec=None):
+    """Every RSK_EINVAL of the four entry points, with outputs untouched by a rejected call; n == 0."""
+    L = rc.lib()
+    tabs, a, n = einval_fixture(rc, device, codec)
+    ctx = () if codec is None else (codec._ctx,)
+    tail = (1,) if codec is None else (None,)
+    ref = lambda s: ctypes.byref(s) if s is not None else None  # noqa: E731
+    resolve = L.rsk_conv_resolve_host if codec is None else L.rsk_conv_resolve_batch
+    send = L.rsk_conv_send_host if codec is None else L.rsk_conv_send_batch
+    flush = L.rsk_conv_flush_host if codec is None else L.rsk_conv_flush
+    build = L.rsk_conv_index_build_host if codec is None else L.rsk_conv_index_build
+    outs = ("row", "cnt", "body", "mid", "ok", "dead")
+
+    def untouched():
+        if codec is not None:
+            torch.cuda.synchronize()
+        return all(bool((a[k].cpu().view(torch.uint8) == SENT).all()) for k in outs)
+
+    for label, t, nn, i, o, want in resolve_einval_cases(tabs, a, n):
+        if want == A.OK or (codec is None and "misaligned" in label):  # the host twins take any alignment
+            continue
+        assert resolve(*ctx, ref(t), nn, ref(i), ref(o), *tail) == want, label
+        assert untouched(), label
+    server, client = tabs[(True, True)], tabs[(False, False)]
+    # build
+    for field, val in (("flags", 4), ("capacity", 0), ("capacity", A.CONN_MAX_ROWS + 1), ("state", None), ("conv", None),
+                       ("index", None), ("dst", None), ("id", None)):
+        t = server.abi()
+        setattr(t, field, val)
+        assert build(*ctx, ref(t), None, *tail) == A.EINVAL, field
+    t = server.abi()
+    t.index += 4
+    assert build(*ctx, ref(t), None, *tail) == A.EINVAL and build(*ctx, None, None, *tail) == A.EINVAL
+    # send
+    p = lambda k: a[k].data_ptr()  # noqa: E731
+    so = lambda **kw: A.ConvSendOut(**kw)  # noqa: E731
+    bad_send = [(None, p("row"), None, so(ok=p("ok"))), (server.abi(), None, None, so(ok=p("ok"))),
+                (client.abi(), p("row"), None, so(dst=p("row"))), (client.abi(), p("row"), None, so(id=p("mid"))),
+                (server.abi(), p("row"), None, None)]
+    if codec is not None:  # the host twins take any alignment
+        bad_send.append((server.abi(), p("row"), None, so(id=p("mid") + 4)))
+    for field, val in (("flags", 8), ("capacity", 0), ("state", None), ("cur_out", None)):
+        t = server.abi()
+        setattr(t, field, val)
+        bad_send.append((t, p("row"), p("sent"), so(ok=p("ok"))))
+    for t, row, sent, o in bad_send:
+        assert send(*ctx, ref(t), n, row, sent, ref(o), *tail) == A.EINVAL
+    assert send(*ctx, ref(server.abi()), A.MAX_BATCH + 1, p("row"), None, ref(so(ok=p("ok"))), *tail) == A.EINVAL
+    # flush
+    for field, val in (("flags", 8), ("capacity", 0), ("state", None), ("alive", None), ("cur_in", None), ("cur_out", None),
+                       ("prev_in", None), ("prev_out", None)):
+        t = server.abi()
+        setattr(t, field, val)
+        assert flush(*ctx, ref(t), ref(A.ConvFlushOut()), *tail) == A.EINVAL, field
+    assert flush(*ctx, ref(server.abi()), ref(A.ConvFlushOut(dead_rows=p("dead"))), *tail) == A.EINVAL
+    assert flush(*ctx, ref(server.abi()), None, *tail) == A.EINVAL and flush(*ctx, None, ref(A.ConvFlushOut()), *tail) == A.EINVAL
+    assert untouched()
+    if codec is not None:
+        assert L.rsk_conv_resolve_batch(None, ref(server.abi()), 0, ref(A.ConvResolveIn()), ref(A.ConvResolveOut()), None) == A.EINVAL
+    # n == 0: null arrays pass, the counts are zeroed and a given rst_first is filled
+    rst = filled(4, torch.int32, device)
+    o = A.ConvResolveOut(None, None, p("cnt"), rst.data_ptr(), A.CtlMsgs(n_msg=a["dead"].data_ptr()))
+    assert resolve(*ctx, ref(server.abi()), 0, ref(A.ConvResolveIn()), ref(o), *tail) == A.OK
+    if codec is not None:
+        torch.cuda.synchronize()
+    assert host(a["cnt"], np.uint32)[0] == 0 and host(a["dead"], np.uint32)[0] == 0
+    assert host(rst, np.uint32).tolist() == [NO_RST] * 4
+    a["cnt"].view(torch.uint8).fill_(SENT)
+    assert send(*ctx, ref(server.abi()), 0, None, None, ref(so(n_bad=p("cnt"))), *tail) == A.OK
+    if codec is not None:
+        torch.cuda.synchronize()
+    assert host(a["cnt"], np.uint32)[0] == 0
+    # the valid calls of the table above do run
+    for label, t, nn, i, o, want in resolve_einval_cases(tabs, a, n):
+        if want == A.OK:
+            assert resolve(*ctx, ref(t), nn, ref(i), ref(o), *tail) == A.OK, label
+    if codec is not None:
+        torch.cuda.synchronize()

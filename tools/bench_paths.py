@@ -7,7 +7,11 @@ verify_wire_eth / verify_wire_raw4 (IPv4 + TCP checksum check of the wire packet
 conn_resolve / conn_resolve_64conn / conn_resolve_miss / conn_expand (the connection table: the decoded
 batch against its own connKeys, 64 connections, half of the keys absent; the send side's gather) /
 control_<config> / control_dense / keepalive_flush_28k / keepalive_flush_1m (control packets and the
-keepalive timer on the connection table; the _kind rows write kind and the messages only).
+keepalive timer on the connection table; the _kind rows write kind and the messages only) /
+conv_per_conn / conv_bursts / conv_one / conv_each (+ _nocount) / conv_flush_1m (the conv table: one conv per
+connection of the batch, the same in runs of 37 neighbours, one conv for all packets, another conv per packet
+over 2^20 rows, each with and without the
+cur_in counts; IGroup::Flush over 2^20 rows).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -379,6 +383,52 @@ def main():
             for grid in (256, 2048):
                 ops[f"dense_read_keepalive_flush_{label}@{grid}"] = lambda grid=grid, b=cap * ka_alg: hp.probe_run(
                     1, wiree.data_ptr(), ysink.data_ptr(), b, grid, s.cuda_stream)
+    # conv table (rsk_conv_resolve_batch / rsk_conv_flush): the decoded batch with three conv columns -- one
+    # conv per connection of the batch (conv_per_conn: its own traffic shape, a row per distinct connKey), one
+    # conv for every packet (conv_one), another conv for every packet of a 2^20 window (conv_each, capacity
+    # 2^20, every row LIVE) -- each with and without the cur_in counts (_nocount), and the flush over 2^20
+    # rows.  Yardsticks of the same run: conn_resolve on the same batch, keepalive_flush_1m on as many rows.
+    import dataclasses
+
+    def conv_table(convs):
+        t = rc.ConvTable.alloc(int(convs.numel()), dev)
+        t.conv.copy_(convs)
+        t.state.fill_(A.CONN_LIVE)
+        t.alive.fill_(1)
+        t.rebuild(cx, stream=s)
+        return t
+
+    v_row = torch.empty(n, dtype=torch.int32, device=dev)
+    ctab_conn = conv_table(torch.arange(own_keys.numel(), device=dev, dtype=torch.int32) * 7 + 3)
+    ctab_each = conv_table(torch.arange(1 << 20, device=dev, dtype=torch.int32) * 5 + 1)
+    col_conn = (torch.searchsorted(own_keys, ddec.conn_key).clamp(max=own_keys.numel() - 1) * 7 + 3).to(torch.int32)
+    # bursts: runs of 37 neighbours carry the conv of the run's first packet (the config itself draws a
+    # connection per packet, so its neighbours share nothing)
+    col_burst = col_conn[(torch.arange(n, device=dev, dtype=torch.int64) // 37) * 37]
+    conv_cols = {"conv_per_conn": (ctab_conn, col_conn),
+                 "conv_bursts": (ctab_conn, col_burst),
+                 "conv_one": (ctab_conn, torch.full((n,), 3, dtype=torch.int32, device=dev)),
+                 "conv_each": (ctab_each, ((torch.arange(n, device=dev, dtype=torch.int64) % (1 << 20)) * 5 + 1).to(torch.int32))}
+    for k, (t, col) in conv_cols.items():
+        ops[k] = lambda t=t, col=col: cx.conv_resolve_batch(t, ddec.status, col, v_row, cmd=ddec.cmd, stream=s)
+        ops[k + "_nocount"] = lambda t=dataclasses.replace(t, cur_in=None), col=col: cx.conv_resolve_batch(
+            t, ddec.status, col, v_row, cmd=ddec.cmd, stream=s)
+        t.cur_in.zero_()
+        ops[k]()
+        torch.cuda.synchronize()
+        # every VALID DATA packet found its row and was counted once
+        assert int((v_row != -1).sum().item()) == looked and int(t.cur_in.to(torch.int64).sum().item()) == looked, k
+    assert int(ctab_conn.cur_in[0].item()) == looked  # conv_one ran last on this table: all on one row
+    fl_alive0 = (torch.arange(1 << 20, device=dev) % 5 != 0).to(torch.uint8)
+    fl_dead, fl_nd, fl_na = (torch.empty(k, dtype=torch.int32, device=dev) for k in (1 << 20, 1, 1))
+    ctab_each.cur_out.copy_(ctab_each.cur_in)
+    ops["conv_flush_1m"] = lambda: (ctab_each.alive.copy_(fl_alive0), cx.conv_flush(
+        ctab_each, dead_rows=fl_dead, n_dead=fl_nd, n_alive=fl_na, stream=s))
+    ops["conv_flush_1m"]()
+    torch.cuda.synchronize()
+    conv_rows = {**{k: t.capacity for k, (t, _col) in conv_cols.items()},
+                 "conv_flush_1m": {"rows": 1 << 20, "n_dead": int(fl_nd.item()), "n_alive": int(fl_na.item())}}
+    assert conv_rows["conv_flush_1m"]["n_dead"] == int((fl_alive0 == 0).sum().item())
     nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -440,6 +490,11 @@ def main():
             alg[k] = ctl_alg(base)
         elif base.startswith("keepalive_flush_"):
             alg[k], items[k] = ka_alg, ctl_rows[base]["rows"]
+    # conv: status, cmd, conv read, conv_row written; the flush reads state, alive and the four counters of a
+    # row and writes alive and the two prev words
+    alg.update({k: 1 + 1 + 4 + 4 for k in ops if k.startswith("conv_") and k != "conv_flush_1m"})
+    if "conv_flush_1m" in ops:
+        alg["conv_flush_1m"], items["conv_flush_1m"] = 1 + 1 + 16 + 1 + 8, 1 << 20
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -483,6 +538,18 @@ def main():
             res[f"{k}_over_dense_read"] = round(out[k]["ms"] / min(dr), 3)
         if k.startswith("control_") and "conn_resolve" in out:
             res[f"{k}_over_conn_resolve"] = round(out[k]["ms"] / out["conn_resolve"]["ms"], 3)
+    if any(k.startswith("conv_") for k in out):
+        res["conv_table_rows"] = conv_rows
+        for k in conv_cols:
+            if k in out and k + "_nocount" in out:
+                res[f"{k}_over_nocount"] = round(out[k]["ms"] / out[k + "_nocount"]["ms"], 3)
+            for q in (k, k + "_nocount"):
+                if q in out and "conn_resolve" in out:
+                    res[f"{q}_over_conn_resolve"] = round(out[q]["ms"] / out["conn_resolve"]["ms"], 3)
+        if "conv_one" in out and "conv_per_conn" in out:
+            res["conv_one_over_conv_per_conn"] = round(out["conv_one"]["ms"] / out["conv_per_conn"]["ms"], 3)
+        if "conv_flush_1m" in out and "keepalive_flush_1m" in out:
+            res["conv_flush_1m_over_keepalive_flush_1m"] = round(out["conv_flush_1m"]["ms"] / out["keepalive_flush_1m"]["ms"], 3)
     print(json.dumps(res))
 
 
