@@ -42,6 +42,8 @@
  *   rsk_conn_expand_batch <- INetConn::Output (conn/INetConn.cpp:30-39) handing FakeTcp's TcpInfo mInfo
  *                            (conn/FakeTcp.cpp:14-50) to RawTcp::Output as the packet's addresses, ports,
  *                            ack and flag
+ *   rsk_conn_pick_batch   <- INetGroup::doSend's pick of an alive conn per outgoing packet, the conn to
+ *                            reset excepted (conn/INetGroup.cpp:111-135)
  *   rsk_conn_table        <- INetGroup's mConnMap and the TcpInfo mInfo of each FakeTcp in it
  *   rsk_control_batch     <- IAppGroup::Input's control branches (conn/IAppGroup.cpp:76-96), ConnReset::Input
  *                            (callbacks/ConnReset.cpp:43-90), NetConnKeepAlive::Input
@@ -636,8 +638,8 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
  * one opaque index, so a batch carries connection indices only:
  *   receive  parse_decode -> verify -> rsk_conn_resolve_batch -> conn[i], the conn / delivered columns of
  *            rsk_tcp_recv_ack_batch(conn, hit, tcp->seq, capacity, tab.ack)
- *   send     rsk_conn_expand_batch(conn) -> src, dst, sp, dp, ack, flag (rsk_wire_in) and conn_key, id
- *            (rsk_encode_in); seq and ip_id from rsk_tcp_send_seq_batch(conn, status, capacity, tab.seq, ...)
+ *   send     rsk_conn_pick_batch -> conn[i]; rsk_conn_expand_batch(conn) -> src, dst, sp, dp, ack, flag
+ *            (rsk_wire_in) and conn_key, id (rsk_encode_in); seq and ip_id from rsk_tcp_send_seq_batch(conn, status, capacity, tab.seq, ...)
  * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
  * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
  * incremental insert or erase); an index that was not rebuilt after such a change gives lookups of
@@ -713,8 +715,8 @@ int rsk_conn_resolve_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, 
  * iff conn[i] < capacity and the row is LIVE and ALIVE; then every given column receives the row's
  * value (ack as it is when the kernel runs: stream-ordered behind an earlier rsk_tcp_recv_ack_batch).
  * Otherwise ok[i] = 0 and every given column receives zero: the caller picked a dead conn, which the
- * reference's doSend drops before picking again (conn/INetGroup.cpp:111-135; the pick itself stays on
- * the host, rand() is not reproducible on the device).  *n_bad = the packets with ok == 0 (written, not
+ * reference's doSend drops before picking again (conn/INetGroup.cpp:111-135; the pick itself is
+ * rsk_conn_pick_batch below, whose conn column never names such a row).  *n_bad = the packets with ok == 0 (written, not
  * accumulated).  No scratch, one memset node and one kernel, as the resolve.
  * RSK_EINVAL: a NULL ctx, tab, out or tab->state; a NULL conn or ok with n > 0; an output column whose
  * table column is NULL; an id column (the table's or out->id) that is not 8-B aligned when out->id is
@@ -738,6 +740,80 @@ int rsk_conn_resolve_host(const rsk_conn_table *tab, uint32_t n, const rsk_conn_
 int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *conn,
                          const rsk_conn_expand_out *out, int nthreads);
 
+/* ---- the send pick: INetGroup::doSend's choice of a connection per outgoing packet ------------------ */
+/* Between rsk_conv_send_batch (the head's conv, dst, id) and rsk_conn_expand_batch (the picked conn's
+ * TcpInfo) the reference runs INetGroup::doSend (conn/INetGroup.cpp:111-135): per packet it draws
+ * rand() % mConns.size(), walks to that conn and takes it if it is Alive(), and for a reset also if it is
+ * not the conn named by keyOfConnToReset.  Here the draw is a column, so the pick is a pure function of
+ * the table, the pick index and the batch.
+ *   Groups.      On a table without RSK_CONN_BY_ID (a client) all rows form one group.  With it (a
+ *                server) a group is the set of rows with one 8-byte id, one SNetGroup per IdBuf.  An id of
+ *                eight zero bytes is an ordinary id.
+ *   Candidates.  A group's rows with both RSK_CONN_LIVE and RSK_CONN_ALIVE, in ascending row order; m is
+ *                their number.
+ *   Packet i:
+ *   1. It is taken iff len == NULL || len[i] > 0 (doSend's nread > 0).  A packet that is not taken gets
+ *      conn[i] = RSK_CONN_NONE, is not counted, and none of its other fields are read.
+ *   2. g = the group of id[i]; without BY_ID the one group, and id is not read.  No group with that id, or
+ *      m == 0: conn[i] = RSK_CONN_NONE and the packet is counted in *n_none (the reference's ERR_NO_CONN).
+ *   3. d = draw[i]; with draw == NULL, d = the upper 32 bits of word i of the splitmix64 stream of `seed`
+ *      (the words rsk_fill_splitmix(seed) writes).
+ *   4. a = avoid_key ? avoid_key[i] : 0.  If a != 0, let r be the row the table's conn index names for
+ *      (id[i], a) -- the resolve's rule; a alone without BY_ID.  If r is a candidate of g, at position p,
+ *      the pick runs over the other m - 1 candidates: m - 1 == 0 gives NONE, counted; otherwise
+ *      k = d % (m - 1), k += (k >= p).  In every other case (a == 0, a key not in the index, a row that is
+ *      no candidate, with BY_ID a key that exists only under another id) k = d % m.
+ *   5. conn[i] = candidate k of g.  With `used` given ([capacity] bytes, zeroed by the caller when it wants)
+ *      used[conn[i]] = 1: plain stores of one value, which tell the host where to clear RSK_CONN_NEW as
+ *      INetConn::Output clears mNew.
+ * Relation to the reference.  With every conn of a group alive and no avoid key the reference takes
+ * element rand() % size of mConns: a table whose rows of a group stand in mConns order, with draw[i] the
+ * i-th rand(), gives the reference's pick exactly.  With dead conns the reference removes the dead one
+ * and draws again: a rejection sampler, uniform over the same candidates, with the same modulo bias of
+ * `%`; the distribution is the same, the number of draws consumed is not (a deliberate deviation, of the
+ * kind of rsk_control_batch's snapshot semantics).  When the only alive conn is the one to avoid the
+ * reference's loop never ends (`continue` at :122 without a removal); here the packet gets NONE and is
+ * counted.  The table is seen as the pick index was last built (a snapshot): which rows are dead is the
+ * host's knowledge already, because it edits `state`.
+ *
+ * The pick index is a separate caller-owned buffer of rsk_conn_pick_bytes(capacity, flags) bytes, 16-B
+ * aligned, rebuilt by the caller after any change to state or id (as rsk_conn_index_build after its
+ * columns); avoid keys also go through tab->index.  A stale or never-built pick index gives an unspecified
+ * row of the table or RSK_CONN_NONE, never an access outside the table or the index.  It has one layout
+ * on host and device: one built on either side and copied to the other is valid there. */
+uint64_t rsk_conn_pick_bytes(uint32_t capacity, uint32_t flags);      /* 0 for a bad capacity / flags */
+/* Builds `pick` from tab->state (and tab->id): a handful of launches on `stream`, set-up rate (one of
+ * them walks the rows in order on a single block).  counts (device [2], may be NULL) receives the groups
+ * that have a candidate and the candidates of the whole table.  No scratch and no host state, but it is
+ * not meant for capture.  RSK_EINVAL: a NULL ctx, tab, tab->state or pick; id missing with BY_ID or not
+ * 8-B aligned; unknown flags; a capacity outside [1, RSK_CONN_MAX_ROWS]; a pick index that is not 16-B
+ * aligned. */
+int rsk_conn_pick_build(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t *pick, uint32_t *counts, void *stream);
+typedef struct rsk_conn_pick_in {
+    const int32_t  *len;        /* [n] optional: the packet is taken iff len[i] > 0; NULL = all taken */
+    const uint8_t  *id;         /* [n*8] the packet's IdBuf (8-B aligned); required with BY_ID, else not read */
+    const uint64_t *avoid_key;  /* [n] optional: keyOfConnToReset, 0 = none (rsk_ctl_msgs.avoid_key) */
+    const uint32_t *draw;       /* [n] optional: the draws; NULL = the splitmix64 stream of `seed` */
+    uint64_t seed;
+} rsk_conn_pick_in;
+typedef struct rsk_conn_pick_out {
+    uint32_t *conn;    /* [n] row, or RSK_CONN_NONE */
+    uint32_t *n_none;  /* [1] optional, written not accumulated: taken packets without a conn */
+    uint8_t  *used;    /* [capacity] optional: used[conn[i]] = 1 */
+} rsk_conn_pick_out;
+/* No scratch and no host state: one memset node (n_none, when given) and one kernel, a linear chain that a
+ * hipGraph captures without a reserve.  n == 0 zeroes a given n_none.  RSK_EINVAL: a NULL ctx, tab, pick,
+ * in or out; a NULL conn with n > 0; id missing (in the table, or in `in` with n > 0) with BY_ID, or one
+ * that is not 8-B aligned; avoid_key given on a table whose conn_key or index is NULL; unknown flags; a
+ * capacity outside [1, RSK_CONN_MAX_ROWS]; a pick index that is not 16-B aligned; n > RSK_MAX_BATCH. */
+int rsk_conn_pick_batch(rsk_ctx *ctx, const rsk_conn_table *tab, const uint32_t *pick, uint32_t n,
+                        const rsk_conn_pick_in *in, const rsk_conn_pick_out *out, void *stream);
+/* Host twins (host pointers throughout; the same rule, outputs and index layout; the id columns at any
+ * alignment; nthreads as rsk_deliver_host, the build runs on the caller's thread; no upper limit on n). */
+int rsk_conn_pick_build_host(const rsk_conn_table *tab, uint32_t *pick, uint32_t *counts, int nthreads);
+int rsk_conn_pick_host(const rsk_conn_table *tab, const uint32_t *pick, uint32_t n, const rsk_conn_pick_in *in,
+                       const rsk_conn_pick_out *out, int nthreads);
+
 /* ---- control packets and the keepalive timer on the connection table ------------------------------ */
 /* Every packet that is not DATA is the reference's per packet: IAppGroup::Input branches on cmd
  * (conn/IAppGroup.cpp:76-96), ConnReset::Input (callbacks/ConnReset.cpp:43-90) and
@@ -745,8 +821,8 @@ int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *
  * body's key up in mConnMap and answer, report the conn or clear a pending request; a FIN / RST packet
  * (RSK_RECV_CLOSE) reaches IAppGroup::ProcessTcpFinOrRst (conn/IAppGroup.cpp:103-116).  The state they
  * touch is the table above, and NetConnKeepAlive::OnFlush (:110-145) is a pass over its rows.
- *   receive  parse_decode -> verify -> resolve -> rsk_control_batch -> (the host picks a conn per
- *            message) -> expand -> send_seq -> rsk_encode_wire_batch
+ *   receive  parse_decode -> verify -> resolve -> rsk_control_batch -> rsk_conn_pick_batch (a conn per
+ *            message, with the messages' id and avoid_key) -> expand -> send_seq -> rsk_encode_wire_batch
  *   timer    rsk_keepalive_flush -> the same message columns, and the rows that timed out
  *
  * rsk_control_batch classifies packet i, reads the body of a control packet at

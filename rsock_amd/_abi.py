@@ -167,6 +167,14 @@ class ConnExpandOut(ctypes.Structure):
                 ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
 
 
+class ConnPickIn(ctypes.Structure):
+    _fields_ = [("len", _vp), ("id", _vp), ("avoid_key", _vp), ("draw", _vp), ("seed", ctypes.c_uint64)]
+
+
+class ConnPickOut(ctypes.Structure):
+    _fields_ = [("conn", _vp), ("n_none", _vp), ("used", _vp)]
+
+
 class ControlIn(ctypes.Structure):
     _fields_ = [("status", _vp), ("cmd", _vp), ("id", _vp), ("conn_key", _vp), ("pay_off", _vp), ("pay_len", _vp),
                 ("arena", _vp), ("base_off", _vp), ("inner_off", _vp), ("tcp_sp", _vp), ("tcp_dp", _vp), ("miss", _vp)]
@@ -289,6 +297,15 @@ SIGNATURES = [
       _vp]),
     ("rsk_conn_expand_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConnTable), ctypes.c_uint32, _vp, ctypes.POINTER(ConnExpandOut), _vp]),
+    ("rsk_conn_pick_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_conn_pick_build", ctypes.c_int, [_vp, ctypes.POINTER(ConnTable), _vp, _vp, _vp]),
+    ("rsk_conn_pick_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), _vp, ctypes.c_uint32, ctypes.POINTER(ConnPickIn), ctypes.POINTER(ConnPickOut),
+      _vp]),
+    ("rsk_conn_pick_build_host", ctypes.c_int, [ctypes.POINTER(ConnTable), _vp, _vp, ctypes.c_int]),
+    ("rsk_conn_pick_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), _vp, ctypes.c_uint32, ctypes.POINTER(ConnPickIn), ctypes.POINTER(ConnPickOut),
+      ctypes.c_int]),
     ("rsk_conn_index_build_host", ctypes.c_int, [ctypes.POINTER(ConnTable), _vp, ctypes.c_int]),
     ("rsk_conn_resolve_host", ctypes.c_int,
      [ctypes.POINTER(ConnTable), ctypes.c_uint32, ctypes.POINTER(ConnResolveIn), ctypes.POINTER(ConnResolveOut),

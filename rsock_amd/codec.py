@@ -311,17 +311,20 @@ class ConnTable:
     ack: torch.Tensor       # the conn_ack of tcp_recv_ack_batch
     flag: torch.Tensor
     index: torch.Tensor     # opaque, rsk_conn_index_bytes bytes
+    pick: torch.Tensor | None = None  # opaque, rsk_conn_pick_bytes bytes: the send pick's index (rebuild_pick)
 
     @classmethod
     def alloc(cls, capacity: int, device, by_id: bool = False) -> "ConnTable":
         nbytes = lib().rsk_conn_index_bytes(capacity, _abi.CONN_BY_ID if by_id else 0)
-        if nbytes == 0:
+        pbytes = lib().rsk_conn_pick_bytes(capacity, _abi.CONN_BY_ID if by_id else 0)
+        if nbytes == 0 or pbytes == 0:
             raise RskError(f"rsk_conn_index_bytes: bad capacity {capacity}")
         cols = {name: torch.zeros(capacity * k, dtype=dt, device=device) for name, dt, k in _CONN_COLUMNS}
         if not by_id:
             cols["id"] = None
         return cls(capacity=int(capacity), by_id=bool(by_id), index=torch.empty(nbytes // 4, dtype=torch.int32,
-                                                                               device=device), **cols)
+                                                                               device=device),
+                   pick=torch.zeros(pbytes // 4, dtype=torch.int32, device=device), **cols)
 
     @property
     def flags(self) -> int:
@@ -340,10 +343,11 @@ class ConnTable:
         return self
 
     def to(self, device) -> "ConnTable":
-        """A copy of every column and of the index on `device` (the index is valid on either side)."""
+        """A copy of every column, of the index and of the pick index on `device` (both are valid on either
+        side)."""
         mv = lambda t: None if t is None else t.to(device, copy=True)  # noqa: E731
         return ConnTable(self.capacity, self.by_id, *[mv(getattr(self, name)) for name, _, _ in _CONN_COLUMNS],
-                         mv(self.index))
+                         mv(self.index), mv(self.pick))
 
     def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
         """rsk_conn_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
@@ -356,9 +360,44 @@ class ConnTable:
         else:
             codec.conn_index_build(self, n_dup=n_dup, stream=stream)
 
+    def rebuild_pick(self, codec: "Codec | None" = None, stream=None, counts: torch.Tensor | None = None) -> None:
+        """rsk_conn_pick_build on `stream` (a device table, with its Codec), or the host twin (a "cpu" table,
+        codec None): the pick index from state (and id); call it after any change to them.  counts [2]
+        receives the groups that have a candidate and the candidates."""
+        if (codec is None) != (self.pick.device.type == "cpu"):
+            raise RskError("ConnTable.rebuild_pick: a device table takes its Codec, a cpu table none")
+        if codec is None:
+            conn_pick_build_host(self, counts=counts)
+        else:
+            codec.conn_pick_build(self, counts=counts, stream=stream)
+
 
 def _np_ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def conn_pick_build_host(tab: ConnTable, counts=None, nthreads: int = 1) -> None:
+    """rsk_conn_pick_build_host on a "cpu" ConnTable: tab.pick from its state (and id) columns; counts [2]
+    (tensor or numpy) receives the groups that have a candidate and the candidates."""
+    _check(lib().rsk_conn_pick_build_host(ctypes.byref(tab.abi()), _ptr(tab.pick), _addr(counts), nthreads),
+           "rsk_conn_pick_build_host")
+
+
+def conn_pick_host(tab: ConnTable, n: int, len=None, id=None, avoid_key=None, draw=None, seed: int = 0,
+                   used: np.ndarray | None = None, nthreads: int = 1):
+    """rsk_conn_pick_host on a "cpu" ConnTable and numpy columns (no GPU): -> (conn uint32 [n], n_none).
+    used [capacity] uint8, when given, gets 1 at every picked row."""
+    c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)  # noqa: E731
+    len, id, avoid_key, draw = c(len, np.int32), c(id, np.uint8), c(avoid_key, np.uint64), c(draw, np.uint32)
+    conn = np.full(max(n, 1), 0xEEEEEEEE, np.uint32)
+    nn = np.full(1, 0xFFFFFFFF, np.uint32)
+    pin = _abi.ConnPickIn(_np_ptr(len), _np_ptr(id), _np_ptr(avoid_key), _np_ptr(draw), seed & 0xFFFFFFFFFFFFFFFF)
+    pout = _abi.ConnPickOut(_np_ptr(conn), _np_ptr(nn), _np_ptr(used))
+    rc = lib().rsk_conn_pick_host(ctypes.byref(tab.abi()), _ptr(tab.pick), n, ctypes.byref(pin), ctypes.byref(pout),
+                                  nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conn_pick_host failed: rc={rc}")
+    return conn[:n], int(nn[0])
 
 
 def conn_resolve_host(tab: ConnTable, status: np.ndarray, conn_key: np.ndarray, cmd: np.ndarray | None = None,
@@ -929,6 +968,25 @@ class Codec:
         gets the LIVE rows that lost their key to a lower row."""
         _check(lib().rsk_conn_index_build(self._ctx, ctypes.byref(tab.abi()), _ptr(n_dup), _stream(stream)),
                "rsk_conn_index_build")
+
+    def conn_pick_build(self, tab: "ConnTable", counts=None, stream=None) -> None:
+        """rsk_conn_pick_build: rebuild tab.pick from its state (and id) columns; counts [2] gets the groups
+        that have a candidate and the candidates."""
+        _check(lib().rsk_conn_pick_build(self._ctx, ctypes.byref(tab.abi()), _ptr(tab.pick), _ptr(counts),
+                                         _stream(stream)), "rsk_conn_pick_build")
+
+    def conn_pick_batch(self, tab: "ConnTable", conn, len=None, id=None, avoid_key=None, draw=None, seed: int = 0,
+                        n_none=None, used=None, stream=None) -> None:
+        """INetGroup::doSend's pick for conn.numel() packets to send (rsk_conn_pick_batch): conn[i] = a
+        LIVE | ALIVE row of packet i's group (all rows; with a by_id table the rows of id[i]) chosen by
+        draw[i] (None: the splitmix64 stream of `seed`), never the row of avoid_key[i]; CONN_NONE for a
+        packet with len[i] <= 0 and, counted in n_none [1], for one whose group has no such row.  used
+        [capacity] gets 1 at every picked row.  The table is seen as rebuild_pick last saw it."""
+        n = conn.numel()
+        pin = _abi.ConnPickIn(_ptr(len), _ptr(id), _ptr(avoid_key), _ptr(draw), seed & 0xFFFFFFFFFFFFFFFF)
+        pout = _abi.ConnPickOut(_ptr(conn), _ptr(n_none), _ptr(used))
+        _check(lib().rsk_conn_pick_batch(self._ctx, ctypes.byref(tab.abi()), _ptr(tab.pick), n, ctypes.byref(pin),
+                                         ctypes.byref(pout), _stream(stream)), "rsk_conn_pick_batch")
 
     def conn_resolve_batch(self, tab: "ConnTable", status, conn_key, conn, cmd=None, id=None, hit=None, miss=None,
                            n_miss=None, stream=None) -> None:

@@ -46,6 +46,7 @@ struct rsk_ctx {
     // encode path (rsk_encode_batch): 0 = chosen per call from the previous batch's statistic, else
     // RSK_ENC_PATH_* (rsk_set_encode_path)
     int enc_path = 0;
+    int pick_path = 0;  // rsk__set_pick_path (rsk_pick.hip)
     int copy_k = 0;  // the two-pass copy's packets per wave (-1: output-stationary; 0: by the sampled statistic; rsk__set_copy_k)
     // per output-stationary call: the value k_encode_heads_os flags a failed layout check with (calls on
     // different streams of one context draw from it concurrently)

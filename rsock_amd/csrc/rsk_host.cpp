@@ -2,7 +2,7 @@
 // the 32-B decode slots of received frames and assembling frames from encoded header slots and
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
 // (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
-// (rsk_conn_*_host) with its control packets and keepalive timer (rsk_control_host,
+// (rsk_conn_*_host) with its send pick (rsk_conn_pick_*host), its control packets and keepalive timer (rsk_control_host,
 // rsk_keepalive_flush_host) and of the conv table (rsk_conv_*_host); the single-frame slot staging, the capture filter's text form and the connection
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
@@ -13,6 +13,7 @@
 
 #include "../../include/rsk_codec.h"
 #include "rsk_conn.h"
+#include "rsk_pick.h"
 
 namespace {
 
@@ -294,6 +295,134 @@ extern "C" int rsk_conn_expand_host(const rsk_conn_table *t, uint32_t n, const u
         bt->fetch_add(nb, std::memory_order_relaxed);
     });
     if (out->n_bad) *out->n_bad = bad_total.load();
+    return RSK_OK;
+}
+
+// ---- the send pick (rsk_conn_pick_build / rsk_conn_pick_batch): the host twins; layout in rsk_pick.h ----
+namespace {
+
+struct HostPick {
+    const uint32_t *w;
+    rsk::PickLayout l;
+    uint32_t word(uint32_t i) const { return w[i]; }
+    rsk::PickGroup group(uint32_t s) const {
+        rsk::PickGroup g;
+        std::memcpy(&g, w + l.group + 4ull * s, sizeof g);
+        return g;
+    }
+    uint32_t cand(uint32_t i) const { return w[l.cand + i]; }
+    uint32_t pos(uint32_t r) const { return w[l.pos + r]; }
+};
+
+bool pick_tab_ok(const rsk_conn_table *t) {
+    return conn_tab_ok(t) && (!(t->flags & RSK_CONN_BY_ID) || t->id);
+}
+
+}  // namespace
+
+extern "C" uint64_t rsk_conn_pick_bytes(uint32_t capacity, uint32_t flags) {
+    if ((flags & ~RSK_CONN_BY_ID) || capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    return 4ull * rsk::pick_layout(capacity, (flags & RSK_CONN_BY_ID) != 0).words;
+}
+
+extern "C" int rsk_conn_pick_build_host(const rsk_conn_table *t, uint32_t *pick, uint32_t *counts, int /*nthreads*/) {
+    constexpr uint8_t kUp = RSK_CONN_LIVE | RSK_CONN_ALIVE;
+    if (!pick_tab_ok(t) || !t->state || !pick) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(pick) & 15u) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    const uint32_t cap = t->capacity, slots = rsk::conn_slots(cap);
+    const rsk::PickLayout l = rsk::pick_layout(cap, by_id);
+    std::memset(pick, 0, 4ull * rsk::kPickHdr);
+    std::memset(pick + l.cand, 0xFF, 4ull * (l.group - l.cand));  // cand, pos and lead: kConnEmpty
+    std::memset(pick + l.group, 0, 4ull * (l.words - l.group));
+    rsk::PickGroup *grp = reinterpret_cast<rsk::PickGroup *>(pick + l.group);  // 16-B aligned with pick
+    uint32_t *lead = pick + l.lead;
+    auto up = [&](uint32_t r) { return (t->state[r] & kUp) == kUp; };
+    // the entry of a candidate row's IdBuf (taken by the first pass below)
+    auto slot_of = [&](uint64_t id) {
+        uint32_t s = rsk::conn_home(0ull, id, slots);
+        while (lead[s] != rsk::kConnEmpty && grp[s].id != id) s = rsk::conn_next(s, slots);
+        return s;
+    };
+    uint32_t total = 0, groups = 0;
+    if (by_id) {
+        for (uint32_t r = 0; r < cap; ++r) {  // the groups and their counts
+            if (!up(r)) continue;
+            const uint64_t id = load64(t->id + 8ull * r);
+            const uint32_t s = slot_of(id);
+            if (lead[s] == rsk::kConnEmpty) { lead[s] = r; grp[s].id = id; }
+            ++grp[s].cnt;
+        }
+        for (uint32_t r = 0; r < cap; ++r) {  // their offsets, in the order of their lowest rows
+            if (!up(r)) continue;
+            const uint32_t s = slot_of(load64(t->id + 8ull * r));
+            if (lead[s] != r) continue;
+            grp[s].off = total;
+            total += grp[s].cnt;
+            grp[s].cnt = 0;  // counts up again as the rows take their positions
+            ++groups;
+        }
+    }
+    for (uint32_t r = 0; r < cap; ++r) {
+        if (!up(r)) continue;
+        uint32_t off = 0, p;
+        if (by_id) {
+            rsk::PickGroup &g = grp[slot_of(load64(t->id + 8ull * r))];
+            off = g.off;
+            p = g.cnt++;
+        } else {
+            p = total++;
+        }
+        pick[l.pos + r] = p;
+        pick[l.cand + off + p] = r;
+    }
+    if (!by_id) groups = total != 0u;
+    pick[0] = total;
+    pick[1] = groups;
+    if (counts) { counts[0] = groups; counts[1] = total; }
+    return RSK_OK;
+}
+
+extern "C" int rsk_conn_pick_host(const rsk_conn_table *t, const uint32_t *pick, uint32_t n, const rsk_conn_pick_in *in,
+                                  const rsk_conn_pick_out *out, int nthreads) {
+    if (!in || !out || !pick || !pick_tab_ok(t)) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(pick) & 15u) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    if (in->avoid_key && (!t->conn_key || !t->index)) return RSK_EINVAL;
+    if (n && (!out->conn || (by_id && !in->id))) return RSK_EINVAL;
+    std::atomic<uint32_t> none_total{0};
+    std::atomic<uint32_t> *nt = &none_total;
+    const rsk_conn_pick_in a = *in;
+    const rsk_conn_pick_out o = *out;
+    const HostConnTab h{t};
+    const uint32_t cap = t->capacity;
+    const HostPick p{pick, rsk::pick_layout(cap, by_id)};
+    for_shards(n, nthreads, [=](uint32_t lo, uint32_t hi) {
+        uint32_t nn = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            if (a.len && a.len[i] <= 0) {  // not taken: nothing else of it is read
+                o.conn[i] = RSK_CONN_NONE;
+                continue;
+            }
+            const uint64_t id = by_id ? load64(a.id + 8ull * i) : 0ull;
+            uint32_t off, m, row = RSK_CONN_NONE;
+            if (rsk::pick_group(p, cap, by_id, id, off, m)) {
+                const uint32_t d = a.draw ? a.draw[i] : (uint32_t)(rsk::pick_splitmix64_at(a.seed, i) >> 32);
+                const uint64_t av = a.avoid_key ? a.avoid_key[i] : 0ull;
+                uint32_t ap = rsk::kConnEmpty;
+                if (av != 0ull) {
+                    const uint32_t r = rsk::conn_lookup(h, cap, by_id, av, id);
+                    if (r != rsk::kConnEmpty) ap = p.pos(r);
+                }
+                row = rsk::pick_row(p, cap, off, m, d, ap);
+            }
+            o.conn[i] = row;
+            if (row == RSK_CONN_NONE) ++nn;
+            else if (o.used) o.used[row] = 1;
+        }
+        nt->fetch_add(nn, std::memory_order_relaxed);
+    });
+    if (out->n_none) *out->n_none = none_total.load();
     return RSK_OK;
 }
 

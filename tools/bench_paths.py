@@ -11,7 +11,11 @@ keepalive timer on the connection table; the _kind rows write kind and the messa
 conv_per_conn / conv_bursts / conv_one / conv_each (+ _nocount) / conv_flush_1m (the conv table: one conv per
 connection of the batch, the same in runs of 37 neighbours, one conv for all packets, another conv per packet
 over 2^20 rows, each with and without the
-cur_in counts; IGroup::Flush over 2^20 rows).
+cur_in counts; IGroup::Flush over 2^20 rows) /
+conn_pick_client (+ _lds) / conn_pick_server / conn_pick_own_one (+ _lds) / conn_pick_own_groups /
+conn_pick_avoid / conn_pick_build_1m (+ _by_id) (the send pick: one group of 10 conns with the candidates from
+global memory and staged in LDS, 64 groups of 10, the batch's own conns as one group and as groups of 10, an
+avoid key on every packet, the index build over 2^20 rows; the host twin with 16 threads beside them).
     python tools/bench_paths.py [--config c3] [--rounds 5] [--reps 10]"""
 import argparse
 import json
@@ -301,6 +305,78 @@ def main():
             for grid in (2048, 8192, 65536):
                 ops[f"dense_read_{name}@{grid}"] = lambda grid=grid, per=per: hp.probe_run(
                     1, wiree.data_ptr(), ysink.data_ptr(), n * per, grid, s.cuda_stream)
+    # the send pick (rsk_conn_pick_batch / rsk_conn_pick_build): a client's one group of 10 conns (rsock's
+    # default port count) with the candidates read from global memory and staged in LDS, a server's 64 groups
+    # of 10, the batch's own conns as one group and as groups of 10, the 64 x 10 table with an avoid key on
+    # every packet, and the build over 2^20 rows.  Draws from the seed (no column).  Yardsticks of the same
+    # run: conn_resolve and conn_expand above; the host twin with 16 threads on the same batch.
+    import ctypes
+    import time
+
+    def pick_table(m, groups, keys=None):
+        """A table of m candidates spread over `groups` IdBufs (0: a client table); every row LIVE | ALIVE."""
+        t = rc.ConnTable.alloc(m, dev, by_id=groups > 0)
+        t.conn_key.copy_(keys if keys is not None else torch.arange(1, m + 1, device=dev, dtype=torch.int64) * 0x9E3779B1)
+        t.state.fill_(A.CONN_LIVE | A.CONN_ALIVE)
+        if groups:
+            gid = (torch.arange(m, device=dev, dtype=torch.int64) % groups + 1) * 0x100000001B3
+            t.id.copy_(gid.view(torch.uint8))
+        t.flag.fill_(0x18)
+        t.rebuild(cx, stream=s)
+        t.rebuild_pick(cx, stream=s)
+        return t
+
+    def group_ids(groups):
+        g = torch.randint(0, groups, (n,), device=dev, generator=gk, dtype=torch.int64)
+        return g, ((g + 1) * 0x100000001B3).view(torch.uint8)
+
+    n_own = int(own_keys.numel())
+    g_own = max(n_own // 10, 1)
+    pk_client, pk_server = pick_table(10, 0), pick_table(640, 64)
+    pk_own1, pk_owng = pick_table(n_own, 0, own_keys), pick_table(n_own, g_own, own_keys)
+    g64, id64 = group_ids(64)
+    _gown, idown = group_ids(g_own)
+    # the avoid key of packet i: a conn of its own group (rows g, g + 64, ... hold group g)
+    av64 = pk_server.conn_key[g64 + 64 * torch.randint(0, 10, (n,), device=dev, generator=gk, dtype=torch.int64)]
+    p_conn, p_nn = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    set_path = rc.lib().rsk__set_pick_path
+    set_path.argtypes, set_path.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
+
+    def pick_op(tab, path=1, **kw):
+        def f():
+            set_path(cx._ctx, path)
+            cx.conn_pick_batch(tab, p_conn, seed=7, n_none=p_nn, stream=s, **kw)
+        return f
+
+    ops["conn_pick_client"] = pick_op(pk_client)
+    ops["conn_pick_client_lds"] = pick_op(pk_client, path=2)
+    ops["conn_pick_server"] = pick_op(pk_server, id=id64)
+    ops["conn_pick_own_one"] = pick_op(pk_own1)
+    ops["conn_pick_own_one_lds"] = pick_op(pk_own1, path=2)  # past the LDS limit: the plain loads plus the test
+    ops["conn_pick_own_groups"] = pick_op(pk_owng, id=idown)
+    ops["conn_pick_avoid"] = pick_op(pk_server, id=id64, avoid_key=av64)
+    pk_1m, pk_1mg = pick_table(1 << 20, 0), pick_table(1 << 20, (1 << 20) // 10)
+    ops["conn_pick_build_1m"] = lambda: cx.conn_pick_build(pk_1m, stream=s)
+    ops["conn_pick_build_1m_by_id"] = lambda: cx.conn_pick_build(pk_1mg, stream=s)
+    pick_check = {}
+    for k in [k for k in ops if k.startswith("conn_pick_") and "build" not in k]:
+        ops[k]()
+        torch.cuda.synchronize()
+        assert int(p_nn.item()) == 0, k
+        pick_check[k] = int(torch.unique(p_conn).numel())
+    assert pick_check["conn_pick_client"] == pick_check["conn_pick_client_lds"] == 10 and pick_check["conn_pick_server"] == 640
+    ops["conn_pick_avoid"]()
+    torch.cuda.synchronize()
+    assert not bool((pk_server.conn_key[p_conn.to(torch.int64)] == av64).any())
+    pick_host = {}
+    for name, tab, idc in (("conn_pick_client", pk_client, None), ("conn_pick_server", pk_server, id64)):
+        ht, hid = tab.to("cpu"), None if idc is None else idc.cpu().numpy()
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            rc.conn_pick_host(ht, n, id=hid, seed=7, nthreads=16)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        pick_host[name] = round(float(np.median(ts)), 3)
     # control packets and the keepalive timer (rsk_control_batch / rsk_keepalive_flush): the decoded batch
     # with its own cmd column against the table of its connKeys (control_<config>: C4 has 5 % control
     # packets, C3 none -- the cost of finding nothing), the same batch with 20 % control packets
@@ -495,6 +571,13 @@ def main():
     alg.update({k: 1 + 1 + 4 + 4 for k in ops if k.startswith("conv_") and k != "conv_flush_1m"})
     if "conv_flush_1m" in ops:
         alg["conv_flush_1m"], items["conv_flush_1m"] = 1 + 1 + 16 + 1 + 8, 1 << 20
+    # pick: id (BY_ID) and the avoid key read, conn written; the build reads state (and id) and writes cand, pos
+    for k in ops:
+        if k.startswith("conn_pick_build"):
+            alg[k], items[k] = 1 + 8 + (8 + 20 if k.endswith("by_id") else 0), 1 << 20
+        elif k.startswith("conn_pick_"):
+            alg[k] = 4 + (8 if k in ("conn_pick_server", "conn_pick_own_groups", "conn_pick_avoid") else 0) + \
+                (8 if k == "conn_pick_avoid" else 0)
     cx.onrecv_batch(w.frame, w.frame_off, w.frame_len, w.dec, stream=s)
     torch.cuda.synchronize()
     if "syncinput_decode" in ops:
@@ -550,6 +633,17 @@ def main():
             res["conv_one_over_conv_per_conn"] = round(out["conv_one"]["ms"] / out["conv_per_conn"]["ms"], 3)
         if "conv_flush_1m" in out and "keepalive_flush_1m" in out:
             res["conv_flush_1m_over_keepalive_flush_1m"] = round(out["conv_flush_1m"]["ms"] / out["keepalive_flush_1m"]["ms"], 3)
+    picks = [k for k in out if k.startswith("conn_pick_")]
+    if picks:
+        res["conn_pick_rows"] = {"client": 10, "server": [64, 10], "own_one": n_own, "own_groups": [g_own, 10],
+                                 "distinct_conns_picked": pick_check}
+        res["conn_pick_host_16t_ms"] = pick_host
+        for k in picks:
+            for y in ("conn_resolve", "conn_expand"):
+                if y in out and "build" not in k:
+                    res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
+            if k in pick_host:
+                res[f"{k}_host_over_device"] = round(pick_host[k] / out[k]["ms"], 1)
     print(json.dumps(res))
 
 
