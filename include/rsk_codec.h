@@ -766,15 +766,21 @@ int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *
  *   5. conn[i] = candidate k of g.  With `used` given ([capacity] bytes, zeroed by the caller when it wants)
  *      used[conn[i]] = 1: plain stores of one value, which tell the host where to clear RSK_CONN_NEW as
  *      INetConn::Output clears mNew.
- * Relation to the reference.  With every conn of a group alive and no avoid key the reference takes
- * element rand() % size of mConns: a table whose rows of a group stand in mConns order, with draw[i] the
- * i-th rand(), gives the reference's pick exactly.  With dead conns the reference removes the dead one
+ * Relation to the reference.  With every conn of a group alive and no avoid key (or one that names no conn
+ * of the group) the reference takes element rand() % size of mConns: a table whose rows of a group stand in
+ * mConns order, with draw[i] the i-th rand(), gives the reference's pick exactly.  mConns is a
+ * std::map<std::string, IConn *> keyed by KeyGenerator::StrForIntKey(key) = std::to_string(key), so its
+ * order is the lexicographic order of the keys' decimal strings ("10" < "100" < "9"), not their numeric
+ * order: exactness is the caller's row layout, and with rows in any other order the picks are the same
+ * distribution over other conns.  With dead conns the reference removes the dead one
  * and draws again: a rejection sampler, uniform over the same candidates, with the same modulo bias of
  * `%`; the distribution is the same, the number of draws consumed is not (a deliberate deviation, of the
  * kind of rsk_control_batch's snapshot semantics).  When the only alive conn is the one to avoid the
  * reference's loop never ends (`continue` at :122 without a removal); here the packet gets NONE and is
  * counted.  The table is seen as the pick index was last built (a snapshot): which rows are dead is the
- * host's knowledge already, because it edits `state`.
+ * host's knowledge already, because it edits `state`.  The reference learns it inside the walk: a conn that a
+ * NETCONN_RST of the same batch marked dead is still a candidate here until the host clears RSK_CONN_ALIVE
+ * and rebuilds the pick index, where the reference's doSend would draw it, remove it and draw again.
  *
  * The pick index is a separate caller-owned buffer of rsk_conn_pick_bytes(capacity, flags) bytes, 16-B
  * aligned, rebuilt by the caller after any change to state or id (as rsk_conn_index_build after its
@@ -852,10 +858,15 @@ int rsk_conn_pick_host(const rsk_conn_table *tab, const uint32_t *pick, uint32_t
  *                 atomicMin);
  *   ka_tries[r]   (in/out, shared with rsk_keepalive_flush) set to RSK_KA_NONE by any KA_RESP whose conn is r.
  * SNAPSHOT SEMANTICS -- a deliberate deviation.  Every lookup of a call sees the table as last indexed.
- * The reference walks the packets one at a time: after a NETCONN_RST of key K that hit (and whose error
- * handler removed the conn), its later packets see K gone.  A packet at or before its row's rst_first
- * gets what the reference gives it; rst_first is what lets a caller redo the tail for the few rows
- * concerned.
+ * The reference walks the packets one at a time.  A NETCONN_RST of key K that hit only marks the conn dead
+ * (INetConn::NotifyErr, conn/INetConn.cpp:49-52): K stays in mConnMap and its later packets still find it --
+ * a KEEP_ALIVE_REQ for K is answered with a RESP, a second reset notifies again -- until a doSend draws the
+ * dead conn and removes it (conn/INetGroup.cpp:129-130) or the group's Flush does; from then on they see K
+ * gone.  So in a batch that sends nothing (no message of this call, no other send of the group meanwhile)
+ * every packet gets what the reference gives it; with sends, a packet at or before its row's rst_first
+ * always does, and a later packet of that row does as long as no send has drawn the row.  rst_first is what
+ * lets a caller redo the tail for the few rows concerned.  (tests/golden/control.npz holds the reference's
+ * own walk, removals included.)
  *
  * Messages to send (rsk_ctl_msgs): an order-stable compacted list, in packet order, of
  *   - one message per KA_REQ: cmd KEEP_ALIVE_RESP, avoid_key 0 when it hit; cmd NETCONN_RST,
@@ -944,6 +955,12 @@ int rsk_control_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, const
  * column), src = r, avoid_key 0, pay_off 8k, pay_len 8; the arrays hold `capacity` entries.  The table's
  * state stays read-only: the host clears ALIVE for the dead rows and rebuilds when it removes them.  No
  * index is read.  The launches and the scratch are rsk_control_batch's (8 B per 1024 rows).
+ * Against the reference's own OnFlush (tests/golden/control.npz) the requests, the timeouts and mReqMap
+ * are the same per flush; the reference emits in mConns order (the keys' decimal strings), this pass in row
+ * order.  One deviation, of the snapshot kind: the reference's requests travel through doSend while it
+ * iterates, so a request carried by a conn that is still new clears that conn's mNew
+ * (INetConn::Output) and, when the iteration reaches it later in the same flush, it is asked already;
+ * here state is read as the call found it and that row is asked one flush later.
  * RSK_EINVAL: a NULL ctx, tab, ka, out, tab->state, tab->conn_key, ka_tries or established_ms; unknown
  * table flags or a capacity outside [1, RSK_CONN_MAX_ROWS]; max_retry outside [1, 254]; a message array
  * without n_msg, dead_rows without n_dead; an id column (the table's or msgs.id) that is not 8-B aligned

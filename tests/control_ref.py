@@ -7,14 +7,15 @@ ConnReset::Input (callbacks/ConnReset.cpp:43-90) reads a 4-byte conv or an 8-byt
 reports ERR_FIN_RST on the key's conn; NetConnKeepAlive::Input (callbacks/NetConnKeepAlive.cpp:37-98)
 answers a request with a response when the key's conn exists and with a NETCONN_RST when not, and a
 response removes the pending request; IAppGroup::ProcessTcpFinOrRst (conn/IAppGroup.cpp:103-116) looks
-KeyForConnInfo up; NetConnKeepAlive::OnFlush / canSendRequest (:110-145, :168-178) is the timer.  The
-reference's ConnReset / NetConnKeepAlive are not compiled into oracle/_ref (the demux harness replaces
-them with recorders), so the body semantics are pinned by this restatement; what the reference does pin
--- which packets take a control branch -- is checked against tests/golden/demux.npz (check_golden_pin).
+KeyForConnInfo up; NetConnKeepAlive::OnFlush / canSendRequest (:110-145, :168-178) is the timer.  These
+restatements are themselves held against the reference's own ConnReset / NetConnKeepAlive
+(tests/golden/control.npz, tests/control_golden.py); which packets take a control branch is also checked
+against tests/golden/demux.npz (check_golden_pin).
 
 Two restatements: snapshot_ref is the ABI's rule (every lookup sees the table as last indexed);
-sequential_ref walks the packets one at a time and removes a conn at the reset that hits it, as the
-reference's error handler does."""
+sequential_ref walks the packets one at a time.  A reset that hits only marks its conn dead
+(INetConn::NotifyErr): the conn leaves the map when a later doSend draws it (conn/INetGroup.cpp:129-130),
+which depends on the draws, so the walk takes the removals as an input."""
 from __future__ import annotations
 
 import dataclasses
@@ -107,20 +108,33 @@ def snapshot_ref(c, tmap, capacity, by_id, ka_tries=None):
                 n_msg=len(msgs["cmd"]), msgs=out_msgs)
 
 
-def sequential_ref(c, tmap, by_id):
-    """The reference's order: one packet at a time, a conn leaving the map at the reset that hits it.
-    -> (kind, arg, conn)."""
+AT_RESET = "at_reset"
+
+
+def sequential_ref(c, tmap, by_id, removed_at=None):
+    """The reference's order: one packet at a time.  A reset that hits calls NotifyErr(ERR_FIN_RST), which
+    marks the conn dead and leaves it in mConnMap: later packets still find it.  It leaves the map when a
+    doSend draws it dead (during the send of some later packet) or at the group's Flush.
+    removed_at: {(id word, key): index of the packet whose send removed the conn} -- the packets after that
+    one see the key gone; None: nothing is removed during the batch (no sends: the walk equals the
+    snapshot); AT_RESET: every conn a reset hits is removed by that very packet, the earliest the reference
+    can lose it (a send right behind the reset draws it).  -> (kind, arg, conn)."""
     n = len(c["status"])
     w = R.id_words(c.get("id"), n)
     live = dict(tmap)
+    at_reset = isinstance(removed_at, str) and removed_at == AT_RESET
+    pending = {} if removed_at is None or at_reset else dict(removed_at)
     kind, arg, conn = np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.full(n, NONE, np.uint32)
     for i in _interesting(c):
+        for key in [key for key, at in pending.items() if at < i]:
+            live.pop(key, None)
+            del pending[key]
         k, a, look = classify(c, i, by_id)
         key = (int(w[i]) if by_id else 0, a)
         row = live.get(key, NONE) if look else NONE
         kind[i], arg[i], conn[i] = k, a, row
-        if row != NONE and k in (A.CTL_NETCONN_RST, A.CTL_TCP_CLOSE):
-            del live[key]  # NotifyErr(ERR_FIN_RST): the group's handler closes and removes the conn
+        if at_reset and row != NONE and k in (A.CTL_NETCONN_RST, A.CTL_TCP_CLOSE):
+            del live[key]
     return kind, arg, conn
 
 
@@ -445,11 +459,15 @@ def scenario_golden(rc, name, device, codec=None):
 
 
 def scenario_sequential(rc, device, codec=None):
-    """server_dense_ctrl: every packet at or before its row's rst_first agrees with the per-packet walk;
-    some packet behind a reset does not (the deviation is real and rst_first finds it)."""
+    """server_dense_ctrl.  With nothing removed during the batch the per-packet walk is the snapshot, packet
+    for packet.  With every reset conn removed at its reset (the earliest the reference can): every packet at
+    or before its row's rst_first agrees with the walk; some packet behind a reset does not (the deviation
+    is real and rst_first finds it)."""
     _g, c, cols, cap, by_id = golden_batch("server_dense_ctrl", wild=codec is None)
     got, _want, _tab, tmap = check_case(rc, c, cols, cap, by_id, device, codec)
     sk, sa, sc = sequential_ref(c, tmap, by_id)
+    assert np.array_equal(got["kind"], sk) and np.array_equal(got["arg"], sa) and np.array_equal(got["conn"], sc)
+    sk, sa, sc = sequential_ref(c, tmap, by_id, removed_at=AT_RESET)
     row = got["conn"]
     first = np.where(row != NONE, got["rst_first"][np.minimum(row, cap - 1)], NO_RST)
     early = (row == NONE) | (np.arange(len(row)) <= first)

@@ -15,6 +15,7 @@ ORACLE_SO = os.path.join(ROOT, "oracle", "liboracle.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref.so")
 REF_PARSE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_parse.so")
 REF_DEMUX_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_demux.so")
+REF_CONTROL_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_control.so")
 
 _vp = ctypes.c_void_p
 
@@ -460,6 +461,111 @@ class RefDemux:
             else:
                 events.append((kind, pkt, aux))
         return {"per_conn": per_conn, "created": created, "events": events, "ret": log["ret"]}
+
+
+class RefControl:
+    """The reference's own control path, keepalive timer, send pick and conv flush
+    (oracle/_ref/librsk_ref_control.so: the groups of RefDemux with the reference's real ConnReset,
+    NetConnKeepAlive, KeepAliveRouteObserver and Handler; oracle/ref_control_harness.cpp).  RTLD_LAZY as
+    RefParse.  Every run returns its event log as an int64 array [k, 10]: kind, step, conn and seven values
+    (EV_MSG: cmd, body, body length, keyOfConnToReset, draws consumed, the head's IdBuf word, return)."""
+
+    SERVER, CLIENT = 0, 1
+    EV_MSG, EV_NOTIFY, EV_REMOVE, EV_CLOSE = 1, 2, 3, 4
+    ALIVE, NEW = 1, 2
+    ERR_TIMEOUT, ERR_FIN_RST = 1, 2
+    OP_FLUSH, OP_RESP, OP_REMOVE, OP_CLEAR_NEW, OP_ONLINE, OP_GROUP_FLUSH = range(6)
+
+    def __init__(self, path: str = REF_CONTROL_SO):
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        self.L = ctypes.CDLL(path, mode=os.RTLD_LAZY)
+
+    @staticmethod
+    def _c(a, t):
+        return np.ascontiguousarray(np.asarray(a, t))
+
+    def _call(self, fn, *args):
+        """ctypes call: numpy arrays by address, ints as they are (64-bit ones would need argtypes: none here)."""
+        keep = [a for a in args if isinstance(a, np.ndarray)]
+        rc = fn(*[ctypes.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else ctypes.c_uint32(int(a)) for a in args])
+        del keep
+        if rc != 0:
+            raise RuntimeError(f"{fn.__name__} returned {rc}")
+
+    def _group(self, keys, flags, est, id):
+        c = self._c
+        keys = c(keys, np.uint64)
+        est = c(est if est is not None else np.zeros(len(keys)), np.uint64)
+        id = np.frombuffer(bytes(id), np.uint8) if isinstance(id, (bytes, bytearray)) else id
+        return len(keys), keys, c(flags, np.uint8), est, c(id, np.uint8)
+
+    def control(self, shape, keys, flags, id, req, cmd, pid, conv, conn_key, body, body_off, body_len, draws) -> dict:
+        c = self._c
+        nk, keys, flags, est, id = self._group(keys, flags, None, id)
+        rk, rt = c(sorted(req), np.uint64), c([req[k] for k in sorted(req)], np.int32)
+        n = len(cmd)
+        draws = c(draws, np.uint32)
+        ret, look = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ev_cap = 3 * n + nk + 16
+        ev, n_ev = np.zeros((ev_cap, 10), np.int64), np.zeros(1, np.uint32)
+        ok, ot = np.zeros(nk + len(rk) + 1, np.uint64), np.zeros(nk + len(rk) + 1, np.int32)
+        n_o, used = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+        self._call(self.L.ref_control_run, shape, nk, keys, flags, est, id, len(rk), rk, rt, n, c(cmd, np.uint8),
+                   c(pid, np.uint8), c(conv, np.uint32), c(conn_key, np.uint64), c(body, np.uint8), c(body_off, np.uint64),
+                   c(body_len, np.int32), draws, len(draws), ret, look, ev, ev_cap, n_ev, ok, ot, len(ok), n_o, used)
+        k = int(n_o[0])
+        return {"ret": ret, "look": look, "ev": ev[:int(n_ev[0])].copy(), "req_keys": ok[:k].copy(),
+                "req_tries": ot[:k].copy(), "draws_used": int(used[0])}
+
+    def keepalive(self, shape, keys, flags, est, id, req, online, op, arg, draws) -> dict:
+        c = self._c
+        nk, keys, flags, est, id = self._group(keys, flags, est, id)
+        rk, rt = c(sorted(req), np.uint64), c([req[k] for k in sorted(req)], np.int32)
+        op, arg, draws = c(op, np.uint8), c(arg, np.uint64), c(draws, np.uint32)
+        flushes = int((op == self.OP_FLUSH).sum())
+        ev_cap = (flushes + 2) * (2 * nk + 4) + len(op) + 16
+        snap_cap = flushes * (nk + len(rk)) + 16
+        ev, n_ev = np.zeros((ev_cap, 10), np.int64), np.zeros(1, np.uint32)
+        ss, sk, st = np.zeros(snap_cap, np.int64), np.zeros(snap_cap, np.uint64), np.zeros(snap_cap, np.int32)
+        n_s, used = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+        self._call(self.L.ref_keepalive_run, shape, nk, keys, flags, est, id, len(rk), rk, rt, int(bool(online)), len(op),
+                   op, arg, draws, len(draws), ev, ev_cap, n_ev, ss, sk, st, snap_cap, n_s, used)
+        k = int(n_s[0])
+        return {"ev": ev[:int(n_ev[0])].copy(), "snap_step": ss[:k].copy(), "snap_key": sk[:k].copy(),
+                "snap_tries": st[:k].copy(), "draws_used": int(used[0])}
+
+    def dosend(self, shape, keys, flags, id, avoid, draws) -> dict:
+        c = self._c
+        nk, keys, flags, _est, id = self._group(keys, flags, None, id)
+        avoid, draws = c(avoid, np.uint64), c(draws, np.uint32)
+        n = len(avoid)
+        ev_cap = n + nk + 16
+        ev, n_ev = np.zeros((ev_cap, 10), np.int64), np.zeros(1, np.uint32)
+        order, used = np.zeros(nk, np.int32), np.zeros(1, np.uint32)
+        self._call(self.L.ref_dosend_run, shape, nk, keys, flags, id, n, avoid, draws, len(draws), ev, ev_cap, n_ev,
+                   order, used)
+        return {"ev": ev[:int(n_ev[0])].copy(), "order": order, "draws_used": int(used[0])}
+
+    def convflush(self, shape, keys, id, convs, dst, in_off, in_conv, out_off, out_leaf, out_ret, now, draws=(0,)) -> dict:
+        c = self._c
+        nk, keys, flags, _est, id = self._group(keys, np.ones(len(keys), np.uint8), None, id)
+        convs, in_off, in_conv = c(convs, np.uint32), c(in_off, np.uint32), c(in_conv, np.uint32)
+        out_off, out_leaf, out_ret = c(out_off, np.uint32), c(out_leaf, np.uint32), c(out_ret, np.int32)
+        now, draws = c(now, np.uint64), c(draws, np.uint32)
+        rounds, nc = len(now), len(convs)
+        in_ret = np.zeros(max(len(in_conv), 1), np.int32)
+        alive, counters = np.zeros((rounds, nc), np.int8), np.zeros((rounds, nc, 4), np.uint32)
+        ev_cap = nc + nk + 16
+        ev, n_ev, used = np.zeros((ev_cap, 10), np.int64), np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+        self._call(self.L.ref_convflush_run, shape, nk, keys, flags, id, nc, convs, dst, rounds, in_off, in_conv, out_off,
+                   out_leaf, out_ret, now, draws, len(draws), in_ret, alive, counters, ev, ev_cap, n_ev, used)
+        return {"ev": ev[:int(n_ev[0])].copy(), "in_ret": in_ret[:len(in_conv)], "alive": alive, "counters": counters,
+                "draws_used": int(used[0])}
+
+
+def ref_control_available() -> bool:
+    return os.path.exists(REF_CONTROL_SO)
 
 
 def ref_demux_available() -> bool:
