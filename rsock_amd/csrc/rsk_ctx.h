@@ -1,6 +1,7 @@
 // Internal (not installed): the rsk_ctx handle and host helpers shared by the librsk translation
-// units (rsk_kernels.hip: codec; rsk_demux.hip: receive demux; rsk_deliver.hip: payload delivery;
-// rsk_control.hip: control packets and the keepalive timer).
+// units (rsk_kernels.hip, rsk_wire.hip: codec; rsk_demux.hip: receive demux; rsk_deliver.hip: payload
+// delivery; rsk_control.hip: control packets and the keepalive timer), and the few host functions the
+// codec units call across units (at the end).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -270,5 +271,21 @@ inline void free_ws(rsk_ctx *c) {
             if (b.p) (void)hipFree(b.p);
     c->ws.clear();
 }
+
+// ---- host functions of the codec units that another unit calls (not exported from librsk.so) ---------
+struct EncArgs;  // rsk_enc_dev.h
+// AUTO takes a two-pass form (framing encode or wire build) only for batches of at least this many packets
+constexpr uint32_t kTwoPassMinPackets = 16384;
+#pragma GCC visibility push(hidden)
+// rsk_kernels.hip, for rsk_wire.hip: the kernel arguments and the per-set grid of an n-packet call, and
+// AUTO's batch statistic (k_enc_sample is launched from rsk_kernels.hip only).
+bool enc_args(uint32_t n, const rsk_encode_in *in, const rsk_encode_out *out, EncArgs &a);
+unsigned enc_grid(uint64_t n);
+uint32_t sampled_mean(const rsk_ctx *c);
+int enc_path(rsk_ctx *c, uint32_t n, const uint16_t *pay_len, hipStream_t st, const uint64_t *frame_off = nullptr,
+             uint32_t pad = 0u);
+void sample_next(rsk_ctx *c, uint32_t n, const uint16_t *pay_len, hipStream_t st, const uint64_t *frame_off,
+                 uint32_t pad);
+#pragma GCC visibility pop
 
 }  // namespace rsk

@@ -190,7 +190,7 @@ def test_wire_two_pass_chunks_equal_per_set(codec, gpu, eth):
 @pytest.mark.parametrize("cfg,eth,exp", [("c4", False, (2, 4)), ("c4", True, (2, 4)), ("c3", False, (2, 2)),
                                           ("c3", True, (1, 0)), ("c2", False, (1, 0)), ("c2", True, (1, 0))])
 def test_wire_auto_path(gpu, cfg, eth, exp):
-    """AUTO's wire table (rsk_kernels.hip wire_path / wire_k, profiles/r06_wire_paths.json): the per-set
+    """AUTO's wire table (rsk_wire.hip wire_path / wire_k, profiles/r06_wire_paths.json): the per-set
     wire kernels for short frames (C2) and for Ethernet packets of 1400-B payloads (C3), the two-pass
     form with 4 packets per copy wave for mid-length frames (C4) and 2 for RAW4 packets of 1400 B --
     from a fresh context's first call (it samples its own batch) on."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of one kernel in a hipcc -S listing (tools only).
-   python tools/isa_count.py rsock_amd/rsk_kernels.s k_tag_table [--from LINE --to LINE]"""
+   make -C rsock_amd asm && python tools/isa_count.py rsock_amd/build/rsk_kernels.s k_tag_table"""
 import collections
 import re
 import sys
