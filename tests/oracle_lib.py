@@ -16,6 +16,7 @@ REF_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref.so")
 REF_PARSE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_parse.so")
 REF_DEMUX_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_demux.so")
 REF_CONTROL_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_control.so")
+REF_TCPSTATE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_tcpstate.so")
 
 _vp = ctypes.c_void_p
 
@@ -562,6 +563,78 @@ class RefControl:
                    out_leaf, out_ret, now, draws, len(draws), in_ret, alive, counters, ev, ev_cap, n_ev, used)
         return {"ev": ev[:int(n_ev[0])].copy(), "in_ret": in_ret[:len(in_conv)], "alive": alive, "counters": counters,
                 "draws_used": int(used[0])}
+
+
+class RefTcpState:
+    """The reference's own fake-TCP connection state and raw-TCP send (oracle/_ref/librsk_ref_tcpstate.so:
+    FakeTcp, TcpUtil, INetConn, IConn, RConn, RawTcp compiled from /root/reference;
+    oracle/ref_tcpstate_harness.cpp, whose libnet_build_tcp / libnet_build_ipv4 / libnet_write record their
+    arguments).  RTLD_LAZY as RefParse.  One object is K FakeTcp conns over one RConn / RawTcp."""
+
+    SEND, RECV = 0, 1
+    COLS = ("kind", "ret", "n_tcp", "n_ip", "n_write", "conn_seq", "conn_ack", "ip_id_next",
+            "t_sp", "t_dp", "t_seq", "t_ack", "t_control", "t_win", "t_sum", "t_urg", "t_len", "t_payload_s",
+            "t_ptag", "t_payload_set",
+            "i_len", "i_tos", "i_id", "i_frag", "i_ttl", "i_prot", "i_sum", "i_src", "i_dst", "i_payload_set",
+            "i_payload_s", "i_ptag")
+
+    def __init__(self, hash_key: bytes, info, key, ip_id0: int, path: str = REF_TCPSTATE_SO):
+        """info [K, 7] = src, dst, sp, dp, seq, ack, flag (the TcpInfo each FakeTcp is made from), key [K]."""
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        L = self.L = ctypes.CDLL(path, mode=os.RTLD_LAZY)
+        L.ref_ts_open.restype = _vp
+        L.ref_ts_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp]
+        L.ref_ts_run.argtypes = [_vp, ctypes.c_uint32] + [_vp] * 10 + [ctypes.c_uint32]
+        L.ref_ts_state.argtypes = [_vp, _vp, _vp]
+        L.ref_ts_state.restype = None
+        L.ref_ts_close.argtypes = [_vp]
+        L.ref_ts_close.restype = None
+        info = np.ascontiguousarray(np.asarray(info, np.uint32).reshape(-1, 7))
+        key = np.ascontiguousarray(np.asarray(key, np.uint64))
+        assert len(key) == len(info)
+        self.k = len(key)
+        self.state0 = np.zeros((self.k, 2), np.uint32)  # mInfo.seq, mInfo.ack after FakeTcp::Init
+        self.h = L.ref_ts_open(hash_key, len(hash_key), self.k, _p(info), _p(key), ip_id0, _p(self.state0))
+
+    def head_size(self) -> int:
+        return int(self.L.ref_ts_head_size())
+
+    def run(self, kind, conn, a, b, pay_arena, pay_off, conv, id8: bytes, frame_cap: int = 0) -> dict:
+        """The events in order; -> one column per COLS entry (int64) and, with frame_cap, `frames` [n, frame_cap]:
+        the bytes behind libnet_build_tcp's payload pointer."""
+        c = lambda x, t: np.ascontiguousarray(np.asarray(x, t))  # noqa: E731
+        kind, conn, a, b = c(kind, np.uint8), c(conn, np.uint32), c(a, np.uint32), c(b, np.int32)
+        arena, pay_off, conv = c(pay_arena, np.uint8), c(pay_off, np.uint64), c(conv, np.uint32)
+        n = len(kind)
+        assert len(conn) == len(a) == len(b) == len(pay_off) == len(conv) == n
+        sends = kind == self.SEND
+        assert not sends.any() or int((pay_off[sends] + a[sends]).max()) <= len(arena)
+        rec = np.zeros((max(n, 1), len(self.COLS)), np.int64)
+        frames = np.zeros((max(n, 1), frame_cap), np.uint8) if frame_cap else None
+        idb = np.frombuffer(bytes(id8)[:8].ljust(8, b"\0"), np.uint8).copy()
+        rc = self.L.ref_ts_run(self.h, n, _p(kind), _p(conn), _p(a), _p(b), _p(arena), _p(pay_off), _p(conv), _p(idb),
+                               _p(rec), _p(frames), frame_cap)
+        assert rc == 0, rc
+        out = {k: rec[:n, j].copy() for j, k in enumerate(self.COLS)}
+        if frame_cap:
+            out["frames"] = frames[:n]
+        return out
+
+    def state(self):
+        """-> (each conn's mInfo.seq / mInfo.ack as they stand [K, 2], RawTcp::mIpId)."""
+        st, ip = np.zeros((self.k, 2), np.uint32), np.zeros(1, np.uint32)
+        self.L.ref_ts_state(self.h, _p(st), _p(ip))
+        return st, int(ip[0])
+
+    def close(self):
+        if self.h:
+            self.L.ref_ts_close(self.h)
+            self.h = None
+
+
+def ref_tcpstate_available() -> bool:
+    return os.path.exists(REF_TCPSTATE_SO)
 
 
 def ref_control_available() -> bool:
