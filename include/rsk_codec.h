@@ -642,7 +642,8 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
  *            (rsk_wire_in) and conn_key, id (rsk_encode_in); seq and ip_id from rsk_tcp_send_seq_batch(conn, status, capacity, tab.seq, ...)
  * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
  * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
- * incremental insert or erase); an index that was not rebuilt after such a change gives lookups of
+ * incremental insert or erase -- the conv table's rsk_conv_create_batch is the one insert there is, and
+ * erase still means clear LIVE and rebuild); an index that was not rebuilt after such a change gives lookups of
  * the changed keys an unspecified row or RSK_CONN_NONE, never an access outside the table.  The other
  * columns need no rebuild.  The arrays are the caller's and do not move, so a call captured into a
  * hipGraph sees later row edits and rebuilds.
@@ -997,7 +998,9 @@ int rsk_keepalive_flush_host(const rsk_conn_table *tab, const rsk_keepalive *ka,
  * IGroup::Flush (conn/IGroup.cpp:81-107) closes the convs that went quiet.  Here that level is a second
  * table of `capacity` rows in caller-owned device columns, with the rules of the connection table above:
  * the host edits rows with ordinary copies and calls rsk_conv_index_build after any change to state,
- * conv, dst or id; the counter columns need no rebuild.
+ * conv, dst or id; the counter columns need no rebuild.  The one exception is rsk_conv_create_batch below,
+ * which writes the rows of the convs born in a batch and inserts them into the index in place; closing a
+ * conv still means clear LIVE and rebuild.
  *   receive  ... -> rsk_conn_resolve_batch (hit) -> rsk_control_batch (kind, arg) -> rsk_conv_resolve_batch
  *            -> conv_row[i]; rsk_demux_batch / rsk_deliver_batch hand the bytes to the rows
  *   send     rsk_conv_send_batch(conv_row) -> conv, dst, id (rsk_encode_in) -> ... encode ... ->
@@ -1025,7 +1028,7 @@ typedef struct rsk_conv_table {  /* device pointers, caller-owned, `capacity` ro
 } rsk_conv_table;
 
 /* As rsk_conn_index_build: two launches of the same kernel (clear, insert the LIVE rows), no scratch, no
- * incremental insert; *n_dup (device, optional, written) = the LIVE rows that lost their key to a lower
+ * incremental insert (that is rsk_conv_create_batch); *n_dup (device, optional, written) = the LIVE rows that lost their key to a lower
  * row.  RSK_EINVAL: a NULL ctx, tab, state, conv or index; dst / id missing with their flag; unknown
  * flags; a capacity outside [1, RSK_CONN_MAX_ROWS]; an index that is not 16-B aligned; an id column
  * that is not 8-B aligned. */
@@ -1094,6 +1097,78 @@ typedef struct rsk_conv_resolve_out {
 int rsk_conv_resolve_batch(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t n, const rsk_conv_resolve_in *in,
                            const rsk_conv_resolve_out *out, void *stream);
 
+/* Create: the convs born in a batch, made on the device table (SubGroup::OnRecv -> newConn inside the packet
+ * walk, server/SubGroup.cpp:31-68), so that a receive batch ends in conv rows with no host step:
+ *   rsk_conv_resolve_batch (conv_row, unknown) -> rsk_conv_create_batch -> rsk_demux_batch / rsk_deliver_batch
+ * and the host reads n_new, new_rows and n_full after the batch to open the new convs' UDP sockets.  It is
+ * the documented host procedure (list the distinct unknown keys, write rows, rsk_conv_index_build, resolve
+ * the unknown packets again) done in place:
+ *   1. considered: the first u_max packets with unknown[i] == RSK_RECV_VALID, in packet order.  The key
+ *      fields of other packets are never read.
+ *   2. K_0 .. K_{k-1}: the distinct keys (id, dst, conv -- each part only with its flag) among them, in
+ *      first-arrival order.
+ *   3. v_0 < v_1 < ...: the vacant rows (LIVE bit clear).  K_j gets row v_j for j < n_new = min(k, number of
+ *      vacant rows); n_full = k - n_new.
+ *   4. a new row: state = RSK_CONN_LIVE; conv, dst, id of its first packet; where the table has the column
+ *      cur_in = cur_out = prev_in = prev_out = 0 and alive = 1 (a fresh IConn::DataStat, conn/IConn.h:80-84).
+ *      It is inserted into tab->index with rsk_conv_index_build's rule (compare-and-swap on a free entry,
+ *      the lowest row of a key wins) and no rebuild; the insert is the launch after the one that writes the
+ *      rows.  The index bytes may differ from a rebuilt index (probe positions depend on the insertion
+ *      order); every lookup's result is the same.
+ *   5. every packet of the batch -- considered or not -- with unknown[i] == VALID whose key now resolves gets
+ *      conv_row[i] = row, unknown[i] = RSK_RECV_DROP and adds 1 to cur_in[row] when the column is given
+ *      (exact under any skew, combined on chip as the resolve's).  Every other packet's conv_row / unknown
+ *      and every row that was not created stay bytewise untouched.
+ *   6. new_rows[j] = v_j, new_first[j] = the first packet of K_j, for j < n_new; nothing behind them is
+ *      written.  *n_unknown = the packets still unknown; *n_new, *n_full: written, not accumulated.
+ * With u_max below the number of unknown packets the caller calls again while n_unknown > 0 && n_full == 0:
+ * the sequence gives the rows, conv_row and counters of one call with u_max >= n.
+ * CONV_RST packets are not looked at: one that names a conv born in this call keeps conv_row NONE, as under
+ * the snapshot rule above.  The index must be current, as for every lookup: otherwise the results for the
+ * affected keys are unspecified, but no access leaves the table, work or the columns.  n == 0 writes the
+ * given counts (0) and nothing else.
+ * `rows` holds writable aliases of the table's key columns (the table struct's are const): each must equal
+ * the table's pointer, dst / id only with their flag.
+ * work: rsk_conv_create_bytes(u_max, capacity) bytes, 16-B aligned, caller-owned, contents do not matter;
+ * calls that may run concurrently (two streams) need one each.  With m = min(u_max, capacity), P = the
+ * smallest power of two >= max(4, 2 u_max) and M = 2 * ceil(u_max / 64) rounded up to a multiple of 4:
+ * bytes = 4 * (16 + M + P + u_max + 2 m), rounded up to 16.  It depends on u_max and capacity only, never
+ * on n; 0 for u_max == 0, u_max > 2^24 or a bad capacity.
+ * Launches: memset nodes and a linear chain of kernels (list the considered packets; deduplicate them in
+ * work; rank first arrivals and vacant rows; write rows; insert; assign); no block waits on another, nothing
+ * spins, every probe loop is bounded by its table's size.  The per-tile counts live in the control path's
+ * per-stream scratch as the resolve's (rsk_reserve_stream before a capture), everything else in work.
+ * RSK_EINVAL: a NULL ctx, tab, rows, in, out or work; a table a lookup cannot use; rows not aliasing the
+ * table; u_max 0 or > 2^24; with n > 0 a NULL conv_row, unknown or conv, or dst / id missing with their
+ * flag; an id column (in->id, the table's with BY_ID) that is not 8-B aligned or a work that is not 16-B
+ * aligned; n > RSK_MAX_BATCH. */
+uint64_t rsk_conv_create_bytes(uint32_t u_max, uint32_t capacity);
+
+typedef struct rsk_conv_rows {   /* writable aliases of the table's key columns */
+    uint8_t *state; uint32_t *conv; uint32_t *dst; uint8_t *id;
+} rsk_conv_rows;
+
+typedef struct rsk_conv_create_in {
+    const uint8_t  *id;    /* [n*8] the resolve's key columns; each required with its flag, 8-B aligned id */
+    const uint32_t *conv;  /* [n] */
+    const uint32_t *dst;   /* [n] */
+    uint32_t u_max;        /* unknown packets considered per call, in packet order */
+    void *work;            /* rsk_conv_create_bytes(u_max, tab->capacity) bytes */
+} rsk_conv_create_in;
+
+typedef struct rsk_conv_create_out {
+    uint32_t *conv_row;    /* [n] in/out: rsk_conv_resolve_batch's */
+    int8_t   *unknown;     /* [n] in/out: rsk_conv_resolve_batch's */
+    uint32_t *n_unknown;   /* [1] optional, written: packets still unknown afterwards */
+    uint32_t *new_rows;    /* [min(u_max, capacity)] optional: row of the j-th new conv */
+    uint32_t *new_first;   /* [min(u_max, capacity)] optional: packet that created it */
+    uint32_t *n_new;       /* [1] optional, written */
+    uint32_t *n_full;      /* [1] optional, written: distinct considered keys that got no row */
+} rsk_conv_create_out;
+
+int rsk_conv_create_batch(rsk_ctx *ctx, const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
+                          const rsk_conv_create_in *in, const rsk_conv_create_out *out, void *stream);
+
 /* Send: SubGroup::sconnSend / ClientGroup::cconSend set the head's conv, then IConn::Send -> afterSend
  * counts the packet.  ok[i] (optional) = 1 iff conv_row[i] < capacity and the row is LIVE; the given
  * columns conv[i], dst[i], id[8i..] (an rsk_encode_in's) receive the row's values, or zero; *n_bad = the
@@ -1141,6 +1216,9 @@ int rsk_conv_resolve_host(const rsk_conv_table *tab, uint32_t n, const rsk_conv_
 int rsk_conv_send_host(const rsk_conv_table *tab, uint32_t n, const uint32_t *conv_row, const int32_t *sent,
                        const rsk_conv_send_out *out, int nthreads);
 int rsk_conv_flush_host(const rsk_conv_table *tab, const rsk_conv_flush_out *out, int nthreads);
+/* rsk_conv_create_batch's twin: sequential on the caller's thread, the same work buffer (16-B aligned). */
+int rsk_conv_create_host(const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
+                         const rsk_conv_create_in *in, const rsk_conv_create_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

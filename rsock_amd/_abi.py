@@ -214,6 +214,19 @@ class ConvResolveOut(ctypes.Structure):
     _fields_ = [("conv_row", _vp), ("unknown", _vp), ("n_unknown", _vp), ("rst_first", _vp), ("msgs", CtlMsgs)]
 
 
+class ConvRows(ctypes.Structure):
+    _fields_ = [("state", _vp), ("conv", _vp), ("dst", _vp), ("id", _vp)]
+
+
+class ConvCreateIn(ctypes.Structure):
+    _fields_ = [("id", _vp), ("conv", _vp), ("dst", _vp), ("u_max", ctypes.c_uint32), ("work", _vp)]
+
+
+class ConvCreateOut(ctypes.Structure):
+    _fields_ = [("conv_row", _vp), ("unknown", _vp), ("n_unknown", _vp), ("new_rows", _vp), ("new_first", _vp),
+                ("n_new", _vp), ("n_full", _vp)]
+
+
 class ConvSendOut(ctypes.Structure):
     _fields_ = [("conv", _vp), ("dst", _vp), ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
 
@@ -324,6 +337,13 @@ SIGNATURES = [
     ("rsk_conv_resolve_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConvTable), ctypes.c_uint32, ctypes.POINTER(ConvResolveIn), ctypes.POINTER(ConvResolveOut),
       _vp]),
+    ("rsk_conv_create_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_conv_create_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCreateIn),
+      ctypes.POINTER(ConvCreateOut), _vp]),
+    ("rsk_conv_create_host", ctypes.c_int,
+     [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCreateIn),
+      ctypes.POINTER(ConvCreateOut), ctypes.c_int]),
     ("rsk_conv_send_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConvTable), ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ConvSendOut), _vp]),
     ("rsk_conv_flush", ctypes.c_int, [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvFlushOut), _vp]),

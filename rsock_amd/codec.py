@@ -606,6 +606,18 @@ class ConvTable:
         a = getattr(self, name).cpu().numpy()
         return a.view(f"u{a.dtype.itemsize}")
 
+    def abi_rows(self) -> _abi.ConvRows:
+        """The writable aliases of the key columns that rsk_conv_create_batch takes."""
+        return _abi.ConvRows(_ptr(self.state), _ptr(self.conv), _ptr(self.dst), _ptr(self.id))
+
+    def create_work(self, u_max: int) -> torch.Tensor:
+        """The work buffer of conv_create_batch / conv_create_host for at most u_max considered packets
+        per call (rsk_conv_create_bytes), on the table's device; one per stream that runs the call."""
+        nbytes = lib().rsk_conv_create_bytes(u_max, self.capacity)
+        if nbytes == 0:
+            raise RskError(f"rsk_conv_create_bytes: bad u_max {u_max}")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
     def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
         """rsk_conv_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
         table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
@@ -637,6 +649,24 @@ def conv_resolve_host(tab: ConvTable, status, conv, conv_row, cmd=None, hit=None
     rc = lib().rsk_conv_resolve_host(ctypes.byref(tab.abi()), len(status), ctypes.byref(cin), ctypes.byref(cout), nthreads)
     if rc != 0:
         raise RskError(f"rsk_conv_resolve_host failed: rc={rc}")
+
+
+def _conv_create_structs(conv, conv_row, unknown, u_max, work, id, dst, n_unknown, new_rows, new_first, n_new, n_full):
+    cin = _abi.ConvCreateIn(_addr(id), _addr(conv), _addr(dst), int(u_max), _addr(work))
+    cout = _abi.ConvCreateOut(_addr(conv_row), _addr(unknown), _addr(n_unknown), _addr(new_rows), _addr(new_first),
+                              _addr(n_new), _addr(n_full))
+    return cin, cout
+
+
+def conv_create_host(tab: ConvTable, conv, conv_row, unknown, u_max: int, work, id=None, dst=None, n_unknown=None,
+                     new_rows=None, new_first=None, n_new=None, n_full=None, nthreads: int = 1) -> None:
+    """rsk_conv_create_host on a "cpu" ConvTable (no GPU); the arguments of Codec.conv_create_batch."""
+    cin, cout = _conv_create_structs(conv, conv_row, unknown, u_max, work, id, dst, n_unknown, new_rows, new_first,
+                                     n_new, n_full)
+    rc = lib().rsk_conv_create_host(ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()), len(conv_row), ctypes.byref(cin),
+                                    ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conv_create_host failed: rc={rc}")
 
 
 def conv_send_host(tab: ConvTable, conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
@@ -1063,6 +1093,19 @@ class Codec:
                                           n_unknown, rst_first, msgs)
         _check(lib().rsk_conv_resolve_batch(self._ctx, ctypes.byref(tab.abi()), status.numel(), ctypes.byref(cin),
                                             ctypes.byref(cout), _stream(stream)), "rsk_conv_resolve_batch")
+
+    def conv_create_batch(self, tab: "ConvTable", conv, conv_row, unknown, u_max: int, work, id=None, dst=None,
+                          n_unknown=None, new_rows=None, new_first=None, n_new=None, n_full=None, stream=None) -> None:
+        """SubGroup::newConn for the convs born in a batch, on the device table (rsk_conv_create_batch), after
+        conv_resolve_batch left conv_row and unknown: the distinct keys of the first u_max unknown packets
+        take the vacant rows in first-arrival order (new_rows[j], new_first[j], j < n_new; n_full keys got
+        none), the rows go into tab.index in place, and every unknown packet whose key now resolves gets
+        its conv_row, unknown = RECV_DROP and its count in cur_in.  work = tab.create_work(u_max)."""
+        cin, cout = _conv_create_structs(conv, conv_row, unknown, u_max, work, id, dst, n_unknown, new_rows, new_first,
+                                         n_new, n_full)
+        _check(lib().rsk_conv_create_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()),
+                                           conv_row.numel(), ctypes.byref(cin), ctypes.byref(cout), _stream(stream)),
+               "rsk_conv_create_batch")
 
     def conv_send_batch(self, tab: "ConvTable", conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
                         stream=None) -> None:

@@ -13,6 +13,7 @@
 
 #include "../../include/rsk_codec.h"
 #include "rsk_conn.h"
+#include "rsk_conv_create.h"
 #include "rsk_pick.h"
 
 namespace {
@@ -708,6 +709,98 @@ extern "C" int rsk_conv_flush_host(const rsk_conv_table *t, const rsk_conv_flush
     }
     if (out->n_dead) *out->n_dead = n_dead;
     if (out->n_alive) *out->n_alive = n_alive;
+    return RSK_OK;
+}
+
+extern "C" uint64_t rsk_conv_create_bytes(uint32_t u_max, uint32_t capacity) {
+    if (u_max == 0u || u_max > rsk::kCreateMaxU || capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    return 4ull * rsk::create_layout(u_max, capacity).words;
+}
+
+// One walk over the considered packets in packet order -- a first arrival takes the next vacant row and goes
+// into the index at once -- then one over the batch for the packets that now resolve.  The dedup table and
+// the list live in `work` as on the device (rsk_conv_create.h).
+extern "C" int rsk_conv_create_host(const rsk_conv_table *t, const rsk_conv_rows *rows, uint32_t n,
+                                    const rsk_conv_create_in *in, const rsk_conv_create_out *out, int /*nthreads*/) {
+    if (!rows || !in || !out || !conv_tab_lookup_ok(t) || !in->work) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONV_BY_ID) != 0, by_dst = (t->flags & RSK_CONV_BY_DST) != 0;
+    if (rows->state != t->state || rows->conv != t->conv || (by_dst && rows->dst != t->dst) || (by_id && rows->id != t->id))
+        return RSK_EINVAL;
+    if (in->u_max == 0u || in->u_max > rsk::kCreateMaxU) return RSK_EINVAL;
+    if (n && (!out->conv_row || !out->unknown || !in->conv || (by_dst && !in->dst) || (by_id && !in->id))) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(in->work) & 15u) return RSK_EINVAL;
+    if (n > RSK_MAX_BATCH) return RSK_EINVAL;
+    if (out->n_unknown) *out->n_unknown = 0;
+    if (out->n_new) *out->n_new = 0;
+    if (out->n_full) *out->n_full = 0;
+    if (n == 0) return RSK_OK;
+    const uint32_t cap = t->capacity, u = in->u_max < n ? in->u_max : n;
+    const rsk::CreateLayout l = rsk::create_layout(in->u_max, cap);
+    uint32_t *w = static_cast<uint32_t *>(in->work), *dedup = w + l.dedup, *list = w + l.list;
+    auto pkt_key = [&](uint32_t i) {
+        const uint64_t c = in->conv[i];
+        return by_dst ? ((uint64_t)in->dst[i] << 32) | c : c;
+    };
+    auto pkt_id = [&](uint32_t i) { return by_id ? load64(in->id + 8ull * i) : 0ull; };
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n && m < u; ++i)
+        if (out->unknown[i] == RSK_RECV_VALID) list[m++] = i;
+    const uint32_t dslots = rsk::create_slots(m ? m : 1u);  // as many entries as the considered packets need
+    if (m) std::memset(dedup, 0xFF, 4ull * dslots);
+    const HostConvTab h{t};
+    const uint32_t slots = rsk::conn_slots(cap);
+    uint32_t keys = 0, n_new = 0, v = 0;
+    for (uint32_t p = 0; p < m; ++p) {
+        const uint32_t i = list[p];
+        const uint64_t key = pkt_key(i), id = pkt_id(i);
+        bool first = false;
+        for (uint32_t s = rsk::conn_home(key, id, dslots);; s = rsk::conn_next(s, dslots)) {  // at least half is free
+            const uint32_t e = dedup[s];
+            if (e == rsk::kConnEmpty) { dedup[s] = p; first = true; break; }
+            if (pkt_key(list[e]) == key && pkt_id(list[e]) == id) break;
+        }
+        if (!first) continue;
+        ++keys;
+        while (v < cap && (rows->state[v] & RSK_CONN_LIVE)) ++v;
+        if (v == cap) continue;
+        rows->conv[v] = in->conv[i];
+        if (by_dst) rows->dst[v] = in->dst[i];
+        if (by_id) std::memcpy(rows->id + 8ull * v, in->id + 8ull * i, 8);
+        if (t->cur_in) t->cur_in[v] = 0;
+        if (t->cur_out) t->cur_out[v] = 0;
+        if (t->prev_in) t->prev_in[v] = 0;
+        if (t->prev_out) t->prev_out[v] = 0;
+        if (t->alive) t->alive[v] = 1;
+        rows->state[v] = RSK_CONN_LIVE;
+        // rsk_conv_index_build's rule: a free entry, or the lowest row of the key; an entry that is no row
+        // (an index that was never built) ends the walk, as it ends a lookup
+        uint32_t s = rsk::conn_home(key, id, slots);
+        for (uint32_t step = 0; step < slots; ++step, s = rsk::conn_next(s, slots)) {
+            const uint32_t e = t->index[s];
+            if (e == rsk::kConnEmpty) { t->index[s] = v; break; }
+            if (e >= cap) break;
+            if (h.key(e) == key && (!by_id || h.id(e) == id)) {
+                if (v < e) t->index[s] = v;
+                break;
+            }
+        }
+        if (out->new_rows) out->new_rows[n_new] = v;
+        if (out->new_first) out->new_first[n_new] = i;
+        ++n_new;
+        ++v;
+    }
+    uint32_t left = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (out->unknown[i] != RSK_RECV_VALID) continue;
+        const uint32_t row = rsk::conn_lookup(h, cap, by_id, pkt_key(i), pkt_id(i));
+        if (row == RSK_CONN_NONE) { ++left; continue; }
+        out->conv_row[i] = row;
+        out->unknown[i] = RSK_RECV_DROP;
+        if (t->cur_in) ++t->cur_in[row];
+    }
+    if (out->n_unknown) *out->n_unknown = left;
+    if (out->n_new) *out->n_new = n_new;
+    if (out->n_full) *out->n_full = keys - n_new;
     return RSK_OK;
 }
 

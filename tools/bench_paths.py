@@ -12,6 +12,9 @@ conv_per_conn / conv_bursts / conv_one / conv_each (+ _nocount) / conv_flush_1m 
 connection of the batch, the same in runs of 37 neighbours, one conv for all packets, another conv per packet
 over 2^20 rows, each with and without the
 cur_in counts; IGroup::Flush over 2^20 rows) /
+conv_resolve_unknown / conv_create_none / conv_create_born / conv_old_born (rsk_conv_create_batch on the one-conv-
+per-connection column: no packet unknown beside the resolve alone, every conv born in the call on an empty table,
+and the demux + index build + second resolve that the same outcome takes without the call) /
 conn_pick_client (+ _lds) / conn_pick_server / conn_pick_own_one (+ _lds) / conn_pick_own_groups /
 conn_pick_avoid / conn_pick_build_1m (+ _by_id) (the send pick: one group of 10 conns with the candidates from
 global memory and staged in LDS, 64 groups of 10, the batch's own conns as one group and as groups of 10, an
@@ -505,7 +508,74 @@ def main():
     conv_rows = {**{k: t.capacity for k, (t, _col) in conv_cols.items()},
                  "conv_flush_1m": {"rows": 1 << 20, "n_dead": int(fl_nd.item()), "n_alive": int(fl_na.item())}}
     assert conv_rows["conv_flush_1m"]["n_dead"] == int((fl_alive0 == 0).sum().item())
-    nseg = [int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
+    # conv create (rsk_conv_create_batch) on the decoded batch with one conv per connection:
+    #   conv_create_none   no packet unknown (the table holds every conv): what keeping the call in the chain
+    #                      costs; beside it conv_resolve_unknown, the resolve alone that leaves unknown / n_unknown
+    #   conv_create_born   an empty table: every conv of the batch is born in the call (u_max = n)
+    #   conv_old_born      the device work the same outcome takes without the call: rsk_demux_batch on `unknown`,
+    #                      rsk_conv_index_build, the second rsk_conv_resolve_batch on the unknown packets -- on a
+    #                      table whose rows are already written (the device -> host copy of the keys and the row
+    #                      writes between the demux and the build are left out)
+    # The born rows start every call from the same columns: `prep` (outside the timed span) restores them.
+    prep = {}
+    cr_data = (ddec.status == 1) & (ddec.cmd == 0)
+    cr_keys = int(torch.unique(col_conn[cr_data]).numel())  # the convs that DATA packets name
+    cr_cap = min(1 << 20, 1 << (2 * cr_keys - 1).bit_length())
+    cr_row0, cr_unk0 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    cr_row, cr_unk = torch.empty_like(cr_row0), torch.empty_like(cr_unk0)
+    cr_cnt = torch.zeros(4, dtype=torch.int32, device=dev)  # n_unknown, n_new, n_full, the resolve's n_unknown
+    cr_new, cr_first = torch.empty(cr_cap, dtype=torch.int32, device=dev), torch.empty(cr_cap, dtype=torch.int32, device=dev)
+    cr_tab = rc.ConvTable.alloc(cr_cap, dev)
+    cr_tab.rebuild(cx, stream=s)
+    cr_work = cr_tab.create_work(n)
+    cr_none_work = ctab_conn.create_work(n)
+    cx.conv_resolve_batch(cr_tab, ddec.status, col_conn, cr_row0, cmd=ddec.cmd, unknown=cr_unk0, stream=s)
+    cr_old = rc.ConvTable.alloc(cr_cap, dev)  # the old path's table: the rows as the host would have written them
+    cr_old.conv[:cr_keys] = torch.unique(col_conn[cr_data])
+    cr_old.state[:cr_keys] = A.CONN_LIVE
+    cr_old.alive[:cr_keys] = 1
+    cx_cr = rc.Codec(b"hello135", 0)  # the demux of the old path on a context of its own (its table hint)
+    dmx_cr = rc.DemuxBuffers.alloc(n, dev)
+
+    def create_op(tab, work):
+        return lambda: cx.conv_create_batch(tab, col_conn, cr_row, cr_unk, n, work, n_unknown=cr_cnt[0:1], new_rows=cr_new,
+                                            new_first=cr_first, n_new=cr_cnt[1:2], n_full=cr_cnt[2:3], stream=s)
+
+    def cr_reset(tab):
+        def f():
+            tab.state.zero_()
+            tab.rebuild(cx, stream=s)
+            cr_row.copy_(cr_row0)
+            cr_unk.copy_(cr_unk0)
+        return f
+
+    ops["conv_resolve_unknown"] = lambda: cx.conv_resolve_batch(ctab_conn, ddec.status, col_conn, cr_row, cmd=ddec.cmd,
+                                                                unknown=cr_unk, n_unknown=cr_cnt[3:4], stream=s)
+    ops["conv_create_none"] = create_op(ctab_conn, cr_none_work)
+    ops["conv_create_born"] = create_op(cr_tab, cr_work)
+    prep["conv_create_born"] = cr_reset(cr_tab)
+    ops["conv_old_born"] = lambda: (
+        cx_cr.demux_batch(cr_unk0, ddec.cmd, A.DEMUX_CONV, dmx_cr, conv=col_conn, stream=s),
+        cx.conv_index_build(cr_old, stream=s),
+        cx.conv_resolve_batch(cr_old, cr_unk0, col_conn, cr_row, unknown=cr_unk, n_unknown=cr_cnt[3:4], stream=s))
+    ops["conv_resolve_unknown"]()
+    ops["conv_create_none"]()
+    torch.cuda.synchronize()
+    assert cr_cnt.tolist() == [0, 0, 0, 0] and int((cr_row != -1).sum().item()) == looked
+    prep["conv_create_born"]()
+    ops["conv_create_born"]()
+    torch.cuda.synchronize()
+    assert cr_cnt[:3].tolist() == [0, cr_keys, 0] and int((cr_row != -1).sum().item()) == looked
+    assert int(cr_tab.cur_in.to(torch.int64).sum().item()) == looked and int((cr_tab.state == 1).sum().item()) == cr_keys
+    born_rows = cr_row.clone()
+    ops["conv_old_born"]()
+    torch.cuda.synchronize()
+    assert int(cr_cnt[3].item()) == 0 and int(dmx_cr.n_seg.item()) == cr_keys
+    # both ways name one row per conv: the packets of a row are the same packets
+    assert int(torch.unique(torch.stack([born_rows[cr_data], cr_row[cr_data]]).to(torch.int64), dim=1).shape[1]) == cr_keys
+    conv_rows["conv_create"] = {"convs": cr_keys, "capacity": cr_cap, "u_max": n, "unknown_packets": looked,
+                                "work_bytes": int(cr_work.numel()) * 4}
+    nseg =[int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
         # an entry ending in * keeps every path it is a prefix of
@@ -513,6 +583,18 @@ def main():
     times = {k: [] for k in ops}
     for _ in range(args.rounds):
         for k, f in ops.items():
+            if k in prep:  # a call that consumes its inputs: restore them before every call, outside the timed span
+                evs = []
+                for _ in range(args.reps):
+                    prep[k]()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s)
+                    f()
+                    e1.record(s)
+                    evs.append((e0, e1))
+                torch.cuda.synchronize()
+                times[k].append(sum(a.elapsed_time(b) for a, b in evs) / args.reps)
+                continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             for _ in range(args.reps):
@@ -569,6 +651,11 @@ def main():
     # conv: status, cmd, conv read, conv_row written; the flush reads state, alive and the four counters of a
     # row and writes alive and the two prev words
     alg.update({k: 1 + 1 + 4 + 4 for k in ops if k.startswith("conv_") and k != "conv_flush_1m"})
+    # create: unknown read by the count, the list and the assign passes; with every packet unknown also conv read by
+    # the dedup, the two first-arrival passes and the assign, the list written and read three times, conv_row and
+    # unknown written.  The old path: the demux's status, conv, perm and the second resolve's bytes
+    alg.update({"conv_resolve_unknown": 1 + 1 + 4 + 4 + 1, "conv_create_none": 3, "conv_create_born": 3 + 4 * 4 + 4 * 4 + 4 + 1,
+                "conv_old_born": 1 + 4 + 4 + 1 + 4 + 4 + 1})
     if "conv_flush_1m" in ops:
         alg["conv_flush_1m"], items["conv_flush_1m"] = 1 + 1 + 16 + 1 + 8, 1 << 20
     # pick: id (BY_ID) and the avoid key read, conn written; the build reads state (and id) and writes cand, pos
@@ -631,6 +718,10 @@ def main():
                     res[f"{q}_over_conn_resolve"] = round(out[q]["ms"] / out["conn_resolve"]["ms"], 3)
         if "conv_one" in out and "conv_per_conn" in out:
             res["conv_one_over_conv_per_conn"] = round(out["conv_one"]["ms"] / out["conv_per_conn"]["ms"], 3)
+        if "conv_create_none" in out and "conv_resolve_unknown" in out:
+            res["conv_create_none_over_conv_resolve_unknown"] = round(out["conv_create_none"]["ms"] / out["conv_resolve_unknown"]["ms"], 3)
+        if "conv_create_born" in out and "conv_old_born" in out:
+            res["conv_create_born_over_conv_old_born"] = round(out["conv_create_born"]["ms"] / out["conv_old_born"]["ms"], 3)
         if "conv_flush_1m" in out and "keepalive_flush_1m" in out:
             res["conv_flush_1m_over_keepalive_flush_1m"] = round(out["conv_flush_1m"]["ms"] / out["keepalive_flush_1m"]["ms"], 3)
     picks = [k for k in out if k.startswith("conn_pick_")]
