@@ -643,7 +643,8 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
  * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
  * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
  * incremental insert or erase -- the conv table's rsk_conv_create_batch is the one insert there is, and
- * erase still means clear LIVE and rebuild); an index that was not rebuilt after such a change gives lookups of
+ * its rsk_conv_close_batch closes rows on the device by a rebuild of its own; this table's erase is clear LIVE
+ * and rebuild); an index that was not rebuilt after such a change gives lookups of
  * the changed keys an unspecified row or RSK_CONN_NONE, never an access outside the table.  The other
  * columns need no rebuild.  The arrays are the caller's and do not move, so a call captured into a
  * hipGraph sees later row edits and rebuilds.
@@ -998,14 +999,16 @@ int rsk_keepalive_flush_host(const rsk_conn_table *tab, const rsk_keepalive *ka,
  * IGroup::Flush (conn/IGroup.cpp:81-107) closes the convs that went quiet.  Here that level is a second
  * table of `capacity` rows in caller-owned device columns, with the rules of the connection table above:
  * the host edits rows with ordinary copies and calls rsk_conv_index_build after any change to state,
- * conv, dst or id; the counter columns need no rebuild.  The one exception is rsk_conv_create_batch below,
- * which writes the rows of the convs born in a batch and inserts them into the index in place; closing a
- * conv still means clear LIVE and rebuild.
+ * conv, dst or id; the counter columns need no rebuild.  The two exceptions are rsk_conv_create_batch below,
+ * which writes the rows of the convs born in a batch and inserts them into the index in place, and
+ * rsk_conv_close_batch, which clears LIVE for the convs that a reset or the timer closes and leaves the index
+ * without them; the host's clear LIVE and rebuild stays available for any other edit.
  *   receive  ... -> rsk_conn_resolve_batch (hit) -> rsk_control_batch (kind, arg) -> rsk_conv_resolve_batch
- *            -> conv_row[i]; rsk_demux_batch / rsk_deliver_batch hand the bytes to the rows
+ *            -> conv_row[i] (-> rsk_conv_create_batch -> rsk_conv_close_batch -> rsk_conv_create_batch on a
+ *            server); rsk_demux_batch / rsk_deliver_batch hand the bytes to the rows
  *   send     rsk_conv_send_batch(conv_row) -> conv, dst, id (rsk_encode_in) -> ... encode ... ->
  *            rsk_conv_send_batch(conv_row, sent = the encode's status) counts what was sent
- *   timer    rsk_conv_flush -> the rows to close
+ *   timer    rsk_conv_flush -> the rows to close -> rsk_conv_close_batch
  * The key of a row is the 64-bit word ((uint64_t)dst << 32) | conv with RSK_CONV_BY_DST, else conv; with
  * RSK_CONV_BY_ID it is paired with the row's IdBuf word (injective, as the reference's "conv:ip:conv"
  * string inside one SubGroup is).  A client is flags 0, a server both; any combination is valid.  The
@@ -1066,7 +1069,8 @@ int rsk_conv_index_build(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t *n_du
  * SNAPSHOT SEMANTICS, as rsk_control_batch: every lookup sees the table as last indexed; a packet at or
  * before its row's rst_first gets what the reference gives it, and rst_first lets the caller redo the
  * tail; a conv the host creates from `unknown` exists from the next rebuild on.
- * Launches: without a list or a count, memset nodes and one kernel.  With msgs / n_unknown the kernel
+ * Launches: without a list or a count, memset nodes, the fill of a given rst_first (a kernel, so that a captured
+ * chain that reads rst_first again replays exactly) and one kernel.  With msgs / n_unknown the kernel
  * also leaves its tile's number of unknown packets in the control path's per-stream scratch (sized by
  * rsk_reserve_stream), one block scans them, and a third launch writes the list from conv_row's verdicts
  * (the probes run once; the count cannot precede them as in rsk_control_batch, since a message here
@@ -1134,7 +1138,7 @@ int rsk_conv_resolve_batch(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t n, 
  * smallest power of two >= max(4, 2 u_max) and M = 2 * ceil(u_max / 64) rounded up to a multiple of 4:
  * bytes = 4 * (16 + M + P + u_max + 2 m), rounded up to 16.  It depends on u_max and capacity only, never
  * on n; 0 for u_max == 0, u_max > 2^24 or a bad capacity.
- * Launches: memset nodes and a linear chain of kernels (list the considered packets; deduplicate them in
+ * Launches: a linear chain of kernels, the first of which zeroes *n_unknown (list the considered packets; deduplicate them in
  * work; rank first arrivals and vacant rows; write rows; insert; assign); no block waits on another, nothing
  * spins, every probe loop is bounded by its table's size.  The per-tile counts live in the control path's
  * per-stream scratch as the resolve's (rsk_reserve_stream before a capture), everything else in work.
@@ -1169,6 +1173,92 @@ typedef struct rsk_conv_create_out {
 int rsk_conv_create_batch(rsk_ctx *ctx, const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
                           const rsk_conv_create_in *in, const rsk_conv_create_out *out, void *stream);
 
+/* Close: convs closed on the device table, where the reference calls IGroup::CloseConn (conn/IGroup.cpp:126-137):
+ * from IGroup::Flush for the convs that went quiet (conn/IGroup.cpp:81-107), and from ConnReset::OnRecvConvRst
+ * inside the packet walk (callbacks/ConnReset.cpp:67-77), behind which a DATA packet of the same key gets a new
+ * SConn (SubGroup::OnRecv -> newConn, server/SubGroup.cpp:31-68).  A call has exactly one of two forms; in both a
+ * row is closed iff it is LIVE and marked.
+ * TIMER FORM (in->close_rows, n_close, m_max, work; n == 0):
+ *   timer    rsk_conv_flush (dead_rows, n_dead) -> rsk_conv_close_batch(close_rows = dead_rows, n_close = n_dead)
+ *   The marked rows are the first min(*n_close, m_max) entries of close_rows; *n_close is a device word that
+ *   the host need not read.  Entries >= capacity, entries naming a row that is not LIVE and repeated entries
+ *   close nothing extra: a row is closed once.  work: rsk_conv_close_bytes(capacity) bytes (one mark per row,
+ *   rounded up to 16), 16-B aligned, caller-owned, contents do not matter; one per stream that runs the call.
+ *   The packet columns of `out` are not looked at.
+ * RECEIVE FORM (in->rst_first [capacity] and in->ctl_kind [n] as rsk_conv_resolve_batch read and left them;
+ * out->conv_row in/out):
+ *   receive  rsk_conv_resolve_batch -> rsk_conv_create_batch -> rsk_conv_close_batch (HOLD) ->
+ *            rsk_conv_create_batch -> rsk_demux_batch / rsk_deliver_batch
+ *   Row r is marked iff rst_first[r] != 0xFFFFFFFF.  For each packet i whose conv_row[i] is a closed row r, with
+ *   a = rst_first[r]:
+ *     i <= a                                   nothing changes; the reset packet itself keeps conv_row == r;
+ *     i > a, ctl_kind[i] != RSK_CTL_CONV_RST   (a DATA packet that had found the conv) conv_row[i] = NONE,
+ *                                              unknown[i] = RSK_RECV_VALID where the column is given; counted in
+ *                                              n_reopened: the next create makes the reborn conv and routes it;
+ *     i > a, ctl_kind[i] == RSK_CTL_CONV_RST   conv_row[i] = NONE (the reference's lookup finds nothing and
+ *                                              returns -1); counted in n_rst_again.
+ *   *n_unknown is in/out and grows by the reopened packets; n_reopened and n_rst_again are written, not
+ *   accumulated.  No other packet is touched, and ctl_kind[i] of a packet whose conv_row is not a closed row is
+ *   never read.  On a table without RSK_CONV_BY_DST (a client) the resolve never sets rst_first: the call closes
+ *   nothing.  n == 0 closes the marked rows and looks at no packet column.
+ * BOTH FORMS: closed_rows[j] = the j-th closed row in row order (as dead_rows, and as the create takes the
+ * vacant rows), closed_at[j] = its reset's packet index, or 0xFFFFFFFF in the timer form; *n_closed is written,
+ * not accumulated, and nothing behind entry n_closed is written.  state[r] of a closed row loses RSK_CONN_LIVE,
+ * written through rows->state (`rows` aliases the table as in the create).  The key columns, alive and the four
+ * counters of every row stay bytewise untouched (the create resets them when the row is reused): cur_in of a
+ * closed row keeps the counts of its reopened packets.  After the call every lookup gives what
+ * rsk_conv_index_build over the new state gives: the index is rebuilt over the rows that stay (open addressing
+ * without tombstones has no erase in place), by launches that leave at once when nothing closed -- then no byte
+ * of the index, of state or of the packet columns is written.
+ * RSK_CONV_CLOSE_HOLD (receive form only): state keeps LIVE and only the index forgets the closed rows, as if
+ * they were not LIVE.  A create later in the same chain then cannot hand a vacated row to another key, so within
+ * a batch a row names one conv (the old conv's packets up to its reset and a new conv's from its birth on could
+ * otherwise overlap under one row).  After the batch the host clears LIVE for closed_rows; no rebuild is needed,
+ * the index already lacks them.  Until then a held row is LIVE to every other call: rsk_conv_send_batch gives
+ * ok = 1 for it, rsk_conv_flush flushes or lists it, and a rebuild (rsk_conv_index_build, or the next close that
+ * closes something) would insert it again.
+ * DEVIATIONS from the reference's walk that remain: a CONV_RST naming a conv born in the same batch keeps NONE
+ * (the resolve ran before the create); a row's second reset is only counted: n_rst_again > 0 is the conservative
+ * sign of one, and if a DATA packet lay between the two resets the reference closed the reborn conv too -- the
+ * host redoes that row's packets behind the second reset.
+ * Launches: a linear chain of kernels and no memset node (timer form: clear and scatter the marks; count the
+ * closing rows per tile; one block scans; one launch for the packets' pass of the receive form, closed_rows /
+ * closed_at and the clear of the index; one over the rows that clears LIVE and inserts the rows that stay); the
+ * last two leave at once when nothing closes.  No block waits on another, nothing spins, the probe loop is
+ * bounded by the index's size.  The
+ * per-tile counts live in the control path's per-stream scratch (rsk_reserve_stream before a capture).
+ * RSK_EINVAL: a NULL ctx, tab, rows, in or out; a table a lookup cannot use; rows not aliasing the table; both
+ * close_rows and rst_first given, or neither; unknown flags; timer form: a NULL n_close or work, n != 0, HOLD,
+ * or ctl_kind given; receive form: n_close given, or with n > 0 a NULL ctl_kind or conv_row; closed_rows or
+ * closed_at without n_closed; an index or a work that is not 16-B aligned, the table's id column (BY_ID) not
+ * 8-B aligned; n > RSK_MAX_BATCH. */
+#define RSK_CONV_CLOSE_HOLD 0x1u
+uint64_t rsk_conv_close_bytes(uint32_t capacity); /* 0 for a capacity outside [1, RSK_CONN_MAX_ROWS] */
+
+typedef struct rsk_conv_close_in {
+    const uint32_t *close_rows; /* [m_max] timer form: the rows to close, e.g. rsk_conv_flush's dead_rows */
+    const uint32_t *n_close;    /* [1] timer form: device word, e.g. rsk_conv_flush's n_dead */
+    uint32_t m_max;             /* timer form: entries of close_rows */
+    const uint32_t *rst_first;  /* [capacity] receive form: rsk_conv_resolve_batch's */
+    const uint8_t  *ctl_kind;   /* [n] receive form: rsk_control_batch's kind, as the resolve read it */
+    void *work;                 /* timer form: rsk_conv_close_bytes(tab->capacity) bytes */
+    uint32_t flags;             /* RSK_CONV_CLOSE_HOLD */
+} rsk_conv_close_in;
+
+typedef struct rsk_conv_close_out {
+    uint32_t *conv_row;    /* [n] receive form, in/out */
+    int8_t   *unknown;     /* [n] receive form, in/out, optional */
+    uint32_t *n_unknown;   /* [1] receive form, in/out, optional: grows by the reopened packets */
+    uint32_t *closed_rows; /* [capacity] optional */
+    uint32_t *closed_at;   /* [capacity] optional */
+    uint32_t *n_closed;    /* [1] written; required with closed_rows or closed_at */
+    uint32_t *n_reopened;  /* [1] optional, written */
+    uint32_t *n_rst_again; /* [1] optional, written */
+} rsk_conv_close_out;
+
+int rsk_conv_close_batch(rsk_ctx *ctx, const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
+                         const rsk_conv_close_in *in, const rsk_conv_close_out *out, void *stream);
+
 /* Send: SubGroup::sconnSend / ClientGroup::cconSend set the head's conv, then IConn::Send -> afterSend
  * counts the packet.  ok[i] (optional) = 1 iff conv_row[i] < capacity and the row is LIVE; the given
  * columns conv[i], dst[i], id[8i..] (an rsk_encode_in's) receive the row's values, or zero; *n_bad = the
@@ -1197,8 +1287,9 @@ int rsk_conv_send_batch(rsk_ctx *ctx, const rsk_conv_table *tab, uint32_t n, con
  *      prev_in[r] = cur_in[r], prev_out[r] = cur_out[r] (DataStat::Flush).
  * dead_rows is in row order; *n_dead and *n_alive (the LIVE rows alive after the pass: IGroup::Alive() is
  * n_alive != 0) are written, not accumulated.  A conv that goes quiet is therefore marked at one flush
- * and listed at the next, as in the reference.  state stays read-only: the host clears LIVE for the
- * rows it closes and rebuilds.  No index is read.  Launches and scratch are rsk_keepalive_flush's.
+ * and listed at the next, as in the reference.  state stays read-only: rsk_conv_close_batch(close_rows =
+ * dead_rows, n_close = n_dead) closes the listed rows on the device (or the host clears LIVE for them and
+ * rebuilds).  No index is read.  Launches and scratch are rsk_keepalive_flush's.
  * RSK_EINVAL: a NULL ctx, tab, out, state, alive or one of the four counter columns; unknown flags or a
  * bad capacity; dead_rows without n_dead. */
 typedef struct rsk_conv_flush_out {  /* every field optional */
@@ -1219,6 +1310,9 @@ int rsk_conv_flush_host(const rsk_conv_table *tab, const rsk_conv_flush_out *out
 /* rsk_conv_create_batch's twin: sequential on the caller's thread, the same work buffer (16-B aligned). */
 int rsk_conv_create_host(const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
                          const rsk_conv_create_in *in, const rsk_conv_create_out *out, int nthreads);
+/* rsk_conv_close_batch's twin: sequential on the caller's thread, the same work buffer in the timer form. */
+int rsk_conv_close_host(const rsk_conv_table *tab, const rsk_conv_rows *rows, uint32_t n,
+                        const rsk_conv_close_in *in, const rsk_conv_close_out *out, int nthreads);
 
 /* ---- capture filter ------------------------------------------------------- */
 /* RCap::doInit (cap/RCap.cpp:64-88) compiles BuildFilterStr("tcp", srcIp, dstIp, srcPorts, dstPorts,

@@ -53,6 +53,7 @@ KA_NONE = 0xFF
 KA_REQUEST_DELAY_MS = 15000
 KA_MAX_RETRY = 3
 CONV_BY_DST, CONV_BY_ID = 0x1, 0x2
+CONV_CLOSE_HOLD = 0x1
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -227,6 +228,16 @@ class ConvCreateOut(ctypes.Structure):
                 ("n_new", _vp), ("n_full", _vp)]
 
 
+class ConvCloseIn(ctypes.Structure):
+    _fields_ = [("close_rows", _vp), ("n_close", _vp), ("m_max", ctypes.c_uint32), ("rst_first", _vp), ("ctl_kind", _vp),
+                ("work", _vp), ("flags", ctypes.c_uint32)]
+
+
+class ConvCloseOut(ctypes.Structure):
+    _fields_ = [("conv_row", _vp), ("unknown", _vp), ("n_unknown", _vp), ("closed_rows", _vp), ("closed_at", _vp),
+                ("n_closed", _vp), ("n_reopened", _vp), ("n_rst_again", _vp)]
+
+
 class ConvSendOut(ctypes.Structure):
     _fields_ = [("conv", _vp), ("dst", _vp), ("id", _vp), ("ok", _vp), ("n_bad", _vp)]
 
@@ -344,6 +355,13 @@ SIGNATURES = [
     ("rsk_conv_create_host", ctypes.c_int,
      [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCreateIn),
       ctypes.POINTER(ConvCreateOut), ctypes.c_int]),
+    ("rsk_conv_close_bytes", ctypes.c_uint64, [ctypes.c_uint32]),
+    ("rsk_conv_close_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCloseIn),
+      ctypes.POINTER(ConvCloseOut), _vp]),
+    ("rsk_conv_close_host", ctypes.c_int,
+     [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCloseIn),
+      ctypes.POINTER(ConvCloseOut), ctypes.c_int]),
     ("rsk_conv_send_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConvTable), ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ConvSendOut), _vp]),
     ("rsk_conv_flush", ctypes.c_int, [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvFlushOut), _vp]),

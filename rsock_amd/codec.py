@@ -618,6 +618,14 @@ class ConvTable:
             raise RskError(f"rsk_conv_create_bytes: bad u_max {u_max}")
         return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
 
+    def close_work(self) -> torch.Tensor:
+        """The work buffer of the timer form of conv_close_batch / conv_close_host (rsk_conv_close_bytes), on the
+        table's device; one per stream that runs the call."""
+        nbytes = lib().rsk_conv_close_bytes(self.capacity)
+        if nbytes == 0:
+            raise RskError(f"rsk_conv_close_bytes: bad capacity {self.capacity}")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
     def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
         """rsk_conv_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
         table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
@@ -667,6 +675,30 @@ def conv_create_host(tab: ConvTable, conv, conv_row, unknown, u_max: int, work, 
                                     ctypes.byref(cout), nthreads)
     if rc != 0:
         raise RskError(f"rsk_conv_create_host failed: rc={rc}")
+
+
+def _conv_close_structs(close_rows, n_close, m_max, rst_first, ctl_kind, work, hold, conv_row, unknown, n_unknown,
+                        closed_rows, closed_at, n_closed, n_reopened, n_rst_again):
+    if m_max is None:
+        m_max = 0 if close_rows is None else len(close_rows)
+    cin = _abi.ConvCloseIn(_addr(close_rows), _addr(n_close), int(m_max), _addr(rst_first), _addr(ctl_kind), _addr(work),
+                           _abi.CONV_CLOSE_HOLD if hold else 0)
+    cout = _abi.ConvCloseOut(_addr(conv_row), _addr(unknown), _addr(n_unknown), _addr(closed_rows), _addr(closed_at),
+                             _addr(n_closed), _addr(n_reopened), _addr(n_rst_again))
+    return cin, cout
+
+
+def conv_close_host(tab: ConvTable, close_rows=None, n_close=None, m_max: int | None = None, work=None, rst_first=None,
+                    ctl_kind=None, conv_row=None, unknown=None, n_unknown=None, hold: bool = False, closed_rows=None,
+                    closed_at=None, n_closed=None, n_reopened=None, n_rst_again=None, nthreads: int = 1) -> None:
+    """rsk_conv_close_host on a "cpu" ConvTable (no GPU); the arguments of Codec.conv_close_batch."""
+    cin, cout = _conv_close_structs(close_rows, n_close, m_max, rst_first, ctl_kind, work, hold, conv_row, unknown,
+                                    n_unknown, closed_rows, closed_at, n_closed, n_reopened, n_rst_again)
+    n = 0 if conv_row is None else len(conv_row)
+    rc = lib().rsk_conv_close_host(ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()), n, ctypes.byref(cin),
+                                   ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conv_close_host failed: rc={rc}")
 
 
 def conv_send_host(tab: ConvTable, conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
@@ -1106,6 +1138,22 @@ class Codec:
         _check(lib().rsk_conv_create_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()),
                                            conv_row.numel(), ctypes.byref(cin), ctypes.byref(cout), _stream(stream)),
                "rsk_conv_create_batch")
+
+    def conv_close_batch(self, tab: "ConvTable", close_rows=None, n_close=None, m_max: int | None = None, work=None,
+                         rst_first=None, ctl_kind=None, conv_row=None, unknown=None, n_unknown=None, hold: bool = False,
+                         closed_rows=None, closed_at=None, n_closed=None, n_reopened=None, n_rst_again=None,
+                         stream=None) -> None:
+        """IGroup::CloseConn on the device table (rsk_conv_close_batch), in one of two forms.  Timer: close_rows /
+        n_close (conv_flush's dead_rows / n_dead; m_max defaults to len(close_rows)) and work = tab.close_work().
+        Receive: rst_first and ctl_kind as conv_resolve_batch had them, conv_row (unknown, n_unknown) in/out: the
+        rows a CONV_RST hit close, and the packets behind their row's reset go back to NONE -- the DATA ones as
+        unknown = RECV_VALID for the next conv_create_batch.  closed_rows / closed_at [capacity] and n_closed list
+        what closed; with hold the rows keep LIVE and only the index forgets them until the host clears them."""
+        cin, cout = _conv_close_structs(close_rows, n_close, m_max, rst_first, ctl_kind, work, hold, conv_row, unknown,
+                                        n_unknown, closed_rows, closed_at, n_closed, n_reopened, n_rst_again)
+        n = 0 if conv_row is None else conv_row.numel()
+        _check(lib().rsk_conv_close_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()), n,
+                                          ctypes.byref(cin), ctypes.byref(cout), _stream(stream)), "rsk_conv_close_batch")
 
     def conv_send_batch(self, tab: "ConvTable", conv_row, sent=None, conv=None, dst=None, id=None, ok=None, n_bad=None,
                         stream=None) -> None:

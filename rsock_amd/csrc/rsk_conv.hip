@@ -28,7 +28,6 @@ namespace {
 using rsk::gptr;
 using rsk::k_tile_scan;
 using rsk::kScanBlock;
-using rsk::memset_async;
 using rsk::misaligned8;
 using rsk::MsgOut;
 using rsk::RowAgg;
@@ -366,7 +365,7 @@ extern "C" int rsk_conv_resolve_batch(rsk_ctx *c, const rsk_conv_table *t, uint3
     if (!g.ok) return RSK_EDEVICE;
     hipStream_t s = (hipStream_t)stream;
     int r;
-    if (out->rst_first && (r = memset_async(out->rst_first, 0xFF, 4ull * t->capacity, s))) return r;
+    if (out->rst_first && (r = rsk::fill_words_async(out->rst_first, t->capacity, 0xFFFFFFFFu, s))) return r;
     if (n == 0) {
         if ((r = zero_word(out->msgs.n_msg, s))) return r;
         return zero_word(out->n_unknown, s);

@@ -5,8 +5,8 @@
 // atomicMin tie-break (k_index_build, rsk_conn_dev.h), so an insert-only update leaves every lookup valid.
 //
 // A linear chain on the stream; `work` as laid out in rsk_conv_create.h, hdr = the counts between launches:
-//   memset          *n_unknown (0)
-//   k_cc_count      per 2048-packet tile, the packets with unknown == VALID
+//   k_cc_count      per 2048-packet tile, the packets with unknown == VALID; *n_unknown = 0 (a store, not a
+//                   memset node: rsk_tile_dev.h, k_fill_words)
 //   k_tile_scan     their exclusive scan; the total -> hdr[unknown]
 //   k_cc_list       list[p] = the p-th unknown packet, p < u = min(u_max, n): the considered packets; and the
 //                   dedup table cleared -- as many entries as the considered packets need (create_slots), so
@@ -114,6 +114,7 @@ __device__ __forceinline__ uint32_t dedup_slots(uint32_t mcons) {
 __global__ __launch_bounds__(kBlock) void k_cc_count(CreateArgs a) {
     __shared__ uint32_t red[2][kWaves];
     const uint64_t base = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    if (a.n_unknown && blockIdx.x == 0u && threadIdx.x == 0u) *gptr(a.n_unknown) = 0u;  // k_cc_assign, a later launch, adds
     uint32_t c = 0;  // wave-uniform
 #pragma unroll
     for (unsigned k = 0; k < kPer; ++k) {
@@ -312,7 +313,7 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_cc_assign(CreateArgs a) {
     __shared__ uint32_t wave_unk[kWaves];
     __shared__ std::conditional_t<COUNT, RowAgg<kPer>, char> agg;
-    if (gptr(a.hdr)[rsk::kCreateUnknown] == 0u) return;  // uniform over the grid; *n_unknown was zeroed
+    if (gptr(a.hdr)[rsk::kCreateUnknown] == 0u) return;  // uniform over the grid; k_cc_count zeroed *n_unknown
     const uint64_t base = (uint64_t)blockIdx.x * kTile + threadIdx.x;
     bool unk[kPer];
 #pragma unroll
@@ -346,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_assign(CreateArgs a) {
         }
         left += (uint32_t)__popcll(__ballot(unk[k] && row[k] == RSK_CONN_NONE));
     }
-    if (a.n_unknown) {  // the word was zeroed on the stream ahead of the chain; one atomic per block
+    if (a.n_unknown) {  // k_cc_count zeroed the word; one atomic per block
         if ((threadIdx.x & 63u) == 0u) wave_unk[threadIdx.x >> 6] = left;
         __syncthreads();
         if (threadIdx.x == 0u) {
@@ -382,9 +383,8 @@ extern "C" int rsk_conv_create_batch(rsk_ctx *c, const rsk_conv_table *t, const 
     if (!g.ok) return RSK_EDEVICE;
     hipStream_t s = (hipStream_t)stream;
     int r;
-    if ((r = zero_word(out->n_unknown, s))) return r;
     if (n == 0) {
-        if ((r = zero_word(out->n_new, s))) return r;
+        if ((r = zero_word(out->n_unknown, s)) || (r = zero_word(out->n_new, s))) return r;
         return zero_word(out->n_full, s);
     }
     const rsk::CreateLayout l = rsk::create_layout(in->u_max, t->capacity);

@@ -804,6 +804,69 @@ extern "C" int rsk_conv_create_host(const rsk_conv_table *t, const rsk_conv_rows
     return RSK_OK;
 }
 
+extern "C" uint64_t rsk_conv_close_bytes(uint32_t capacity) {
+    if (capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    return ((uint64_t)capacity + 15u) & ~15ull;
+}
+
+// The marks (timer form: in `work`, as on the device), the packets behind their row's reset, then the rows in
+// order; the index is rebuilt over the rows that stay only when a row closed.
+extern "C" int rsk_conv_close_host(const rsk_conv_table *t, const rsk_conv_rows *rows, uint32_t n,
+                                   const rsk_conv_close_in *in, const rsk_conv_close_out *out, int /*nthreads*/) {
+    if (!rows || !in || !out || !conv_tab_lookup_ok(t)) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONV_BY_ID) != 0, by_dst = (t->flags & RSK_CONV_BY_DST) != 0;
+    if (rows->state != t->state || rows->conv != t->conv || (by_dst && rows->dst != t->dst) || (by_id && rows->id != t->id))
+        return RSK_EINVAL;
+    const bool timer = in->close_rows != nullptr, recv = in->rst_first != nullptr;
+    if (timer == recv || (in->flags & ~RSK_CONV_CLOSE_HOLD)) return RSK_EINVAL;
+    const bool hold = (in->flags & RSK_CONV_CLOSE_HOLD) != 0;
+    if (timer && (!in->n_close || !in->work || n != 0u || hold || in->ctl_kind)) return RSK_EINVAL;
+    if (recv && (in->n_close || (n && (!in->ctl_kind || !out->conv_row)))) return RSK_EINVAL;
+    if ((out->closed_rows || out->closed_at) && !out->n_closed) return RSK_EINVAL;
+    if (reinterpret_cast<uintptr_t>(t->index) & 15u) return RSK_EINVAL;
+    if (timer && (reinterpret_cast<uintptr_t>(in->work) & 15u)) return RSK_EINVAL;
+    if (n > RSK_MAX_BATCH) return RSK_EINVAL;
+    const uint32_t cap = t->capacity;
+    uint8_t *mark = timer ? static_cast<uint8_t *>(in->work) : nullptr;
+    if (timer) {
+        std::memset(mark, 0, (size_t)rsk_conv_close_bytes(cap));
+        const uint32_t m = *in->n_close < in->m_max ? *in->n_close : in->m_max;
+        for (uint32_t j = 0; j < m; ++j)
+            if (in->close_rows[j] < cap) mark[in->close_rows[j]] = 1;
+    }
+    auto closes = [&](uint32_t r) {
+        return (rows->state[r] & RSK_CONN_LIVE) && (timer ? mark[r] != 0 : in->rst_first[r] != 0xFFFFFFFFu);
+    };
+    uint32_t n_re = 0, n_again = 0, n_closed = 0;
+    for (uint32_t i = 0; recv && i < n; ++i) {
+        const uint32_t r = out->conv_row[i];
+        if (r >= cap || !closes(r) || i <= in->rst_first[r]) continue;
+        out->conv_row[i] = RSK_CONN_NONE;
+        if (in->ctl_kind[i] == RSK_CTL_CONV_RST) {
+            ++n_again;
+            continue;
+        }
+        if (out->unknown) out->unknown[i] = RSK_RECV_VALID;
+        ++n_re;
+    }
+    std::vector<uint32_t> held;
+    for (uint32_t r = 0; r < cap; ++r) {
+        if (!closes(r)) continue;
+        if (out->closed_rows) out->closed_rows[n_closed] = r;
+        if (out->closed_at) out->closed_at[n_closed] = timer ? 0xFFFFFFFFu : in->rst_first[r];
+        ++n_closed;
+        rows->state[r] = (uint8_t)(rows->state[r] & ~RSK_CONN_LIVE);
+        if (hold) held.push_back(r);
+    }
+    if (n_closed) index_build_host(HostConvTab{t}, t->index, t->state, cap, by_id, nullptr);
+    for (uint32_t r : held) rows->state[r] |= RSK_CONN_LIVE;  // HOLD: only the index forgets the row
+    if (out->n_closed) *out->n_closed = n_closed;
+    if (out->n_reopened) *out->n_reopened = n_re;
+    if (out->n_rst_again) *out->n_rst_again = n_again;
+    if (out->n_unknown) *out->n_unknown += n_re;
+    return RSK_OK;
+}
+
 extern "C" int rsk_stage_capture_slots(uint32_t n, const uint8_t *arena, const uint64_t *cap_off, const uint32_t *cap_len,
                                        uint32_t slot, uint8_t *slots, int nthreads) {
     if (slot < RSK_CAP_SLOT_MIN || (slot & 15u)) return RSK_EINVAL;

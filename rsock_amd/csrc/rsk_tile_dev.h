@@ -212,6 +212,20 @@ inline MsgOut msg_out(const rsk_ctl_msgs &m) {
 }
 inline bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 
+// words 32-bit words at p = v, by a kernel: one thread per word.  What a captured chain fills and reads again
+// (the resolve's rst_first, the close's marks) is filled this way and not by a memset node: replays of a graph
+// were seen to run a byte-pattern memset node of some KB with a stale pattern once other fills had run between
+// them (tests/test_gpu_conv_close.py, the captured chains).
+static __global__ __launch_bounds__(kTileBlock) void k_fill_words(uint32_t *p, uint32_t words, uint32_t v) {
+    const uint32_t g = blockIdx.x * kTileBlock + threadIdx.x;
+    if (g < words) gptr(p)[g] = v;
+}
+inline int fill_words_async(uint32_t *p, uint32_t words, uint32_t v, hipStream_t s) {
+    if (words == 0u) return RSK_OK;
+    hipLaunchKernelGGL(k_fill_words, dim3((words + kTileBlock - 1u) / kTileBlock), dim3(kTileBlock), 0, s, p, words, v);
+    return launch_check("k_fill_words");
+}
+
 inline int memset_async(void *p, int v, size_t bytes, hipStream_t s) {
     hipError_t e = hipMemsetAsync(p, v, bytes, s);
     if (e != hipSuccess) { set_error("hipMemsetAsync", e); return RSK_EDEVICE; }

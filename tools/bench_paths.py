@@ -12,6 +12,8 @@ conv_per_conn / conv_bursts / conv_one / conv_each (+ _nocount) / conv_flush_1m 
 connection of the batch, the same in runs of 37 neighbours, one conv for all packets, another conv per packet
 over 2^20 rows, each with and without the
 cur_in counts; IGroup::Flush over 2^20 rows) /
+conv_close_none / conv_close_rst / conv_close_timer_1m / conv_old_close / conv_old_close_1m (rsk_conv_close_batch
+with no reset hitting, with 1 % of the convs reset, behind the flush of 2^20 rows, and the index rebuild it replaces) /
 conv_resolve_unknown / conv_create_none / conv_create_born / conv_old_born (rsk_conv_create_batch on the one-conv-
 per-connection column: no packet unknown beside the resolve alone, every conv born in the call on an empty table,
 and the demux + index build + second resolve that the same outcome takes without the call) /
@@ -575,6 +577,78 @@ def main():
     assert int(torch.unique(torch.stack([born_rows[cr_data], cr_row[cr_data]]).to(torch.int64), dim=1).shape[1]) == cr_keys
     conv_rows["conv_create"] = {"convs": cr_keys, "capacity": cr_cap, "u_max": n, "unknown_packets": looked,
                                 "work_bytes": int(cr_work.numel()) * 4}
+    # conv close (rsk_conv_close_batch) on the decoded batch with one conv per connection, and behind the flush:
+    #   conv_close_none       receive form, no reset hits: what keeping the call in the chain costs
+    #   conv_close_rst        1 % of the batch's convs reset once (at their first packet), the tails reopened, HOLD;
+    #                         state, index and the packet columns restored outside the timed span
+    #   conv_close_timer_1m   behind conv_flush_1m's dead_rows: a fifth of 2^20 rows close (on a twin of the table's
+    #                         state and index, so that the other rows of this run keep their table)
+    #   conv_old_close(_1m)   the device share of the old path for the same outcome: rsk_conv_index_build over the
+    #                         same capacity (2^20 rows for _1m); the host round trip and the state copy are left out
+    cl_cap = ctab_conn.capacity
+    cl_tab = dataclasses.replace(ctab_conn, state=ctab_conn.state.clone(), index=ctab_conn.index.clone())
+    cl_state0, cl_index0 = cl_tab.state.clone(), cl_tab.index.clone()
+    cl_row0, cl_unk0 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    cx.conv_resolve_batch(cl_tab, ddec.status, col_conn, cl_row0, cmd=ddec.cmd, unknown=cl_unk0, stream=s)
+    torch.cuda.synchronize()
+    cl_row, cl_unk = cl_row0.clone(), cl_unk0.clone()
+    cl_no_rst = torch.full((cl_cap,), -1, dtype=torch.int32, device=dev)
+    cl_kind0 = torch.zeros(n, dtype=torch.uint8, device=dev)
+    found = torch.nonzero(cl_row0 != -1).squeeze(1)
+    first_pkt = torch.full((cl_cap,), n, dtype=torch.int64, device=dev).scatter_reduce(
+        0, cl_row0[found].to(torch.int64), found, "amin")
+    named = torch.nonzero(first_pkt < n).squeeze(1)
+    cl_reset_rows = named[::100]
+    cl_rst = cl_no_rst.clone()
+    cl_rst[cl_reset_rows] = first_pkt[cl_reset_rows].to(torch.int32)
+    cl_kind = cl_kind0.clone()
+    cl_kind[first_pkt[cl_reset_rows]] = A.CTL_CONV_RST
+    cl_cnt = torch.zeros(4, dtype=torch.int32, device=dev)  # n_unknown, n_closed, n_reopened, n_rst_again
+    cl_rows, cl_at = torch.empty(cl_cap, dtype=torch.int32, device=dev), torch.empty(cl_cap, dtype=torch.int32, device=dev)
+
+    def close_op(rst, kind):
+        return lambda: cx.conv_close_batch(cl_tab, rst_first=rst, ctl_kind=kind, conv_row=cl_row, unknown=cl_unk,
+                                           n_unknown=cl_cnt[0:1], hold=True, closed_rows=cl_rows, closed_at=cl_at,
+                                           n_closed=cl_cnt[1:2], n_reopened=cl_cnt[2:3], n_rst_again=cl_cnt[3:4], stream=s)
+
+    def cl_reset():
+        cl_tab.index.copy_(cl_index0)
+        cl_row.copy_(cl_row0)
+        cl_unk.copy_(cl_unk0)
+        cl_cnt.zero_()
+
+    ops["conv_close_none"] = close_op(cl_no_rst, cl_kind0)
+    ops["conv_close_rst"] = close_op(cl_rst, cl_kind)
+    prep["conv_close_rst"] = cl_reset
+    ops["conv_old_close"] = lambda: cx.conv_index_build(cl_tab, stream=s)
+    cl_each = dataclasses.replace(ctab_each, state=ctab_each.state.clone(), index=ctab_each.index.clone())
+    cl_each_state0, cl_each_index0 = cl_each.state.clone(), cl_each.index.clone()
+    cl_each_work = cl_each.close_work()
+    cl_each_rows, cl_each_n = torch.empty(1 << 20, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    ops["conv_close_timer_1m"] = lambda: cx.conv_close_batch(cl_each, close_rows=fl_dead, n_close=fl_nd, work=cl_each_work,
+                                                             closed_rows=cl_each_rows, n_closed=cl_each_n, stream=s)
+    prep["conv_close_timer_1m"] = lambda: (cl_each.state.copy_(cl_each_state0), cl_each.index.copy_(cl_each_index0))
+    cl_old_1m = dataclasses.replace(ctab_each, index=ctab_each.index.clone())
+    ops["conv_old_close_1m"] = lambda: cx.conv_index_build(cl_old_1m, stream=s)
+    ops["conv_close_none"]()
+    torch.cuda.synchronize()
+    assert cl_cnt.tolist() == [0, 0, 0, 0] and torch.equal(cl_row, cl_row0) and torch.equal(cl_tab.index, cl_index0)
+    cl_reset()
+    ops["conv_close_rst"]()
+    torch.cuda.synchronize()
+    cl_tail = int(((cl_row0 != -1) & (cl_row == -1)).sum().item())
+    assert cl_cnt.tolist() == [cl_tail, int(cl_reset_rows.numel()), cl_tail, 0] and cl_tail > 0
+    assert torch.equal(cl_rows[:cl_reset_rows.numel()].to(torch.int64), cl_reset_rows) and torch.equal(cl_tab.state, cl_state0)
+    cl_reset()
+    ops["conv_close_timer_1m"]()
+    torch.cuda.synchronize()
+    assert int(cl_each_n.item()) == conv_rows["conv_flush_1m"]["n_dead"]
+    assert torch.equal(cl_each_rows[:int(cl_each_n.item())], fl_dead[:int(cl_each_n.item())])
+    assert int((cl_each.state == 1).sum().item()) == (1 << 20) - int(cl_each_n.item())
+    prep["conv_close_timer_1m"]()
+    conv_rows["conv_close"] = {"capacity": cl_cap, "convs_reset": int(cl_reset_rows.numel()), "packets_reopened": cl_tail,
+                               "timer_rows": 1 << 20, "timer_closed": int(cl_each_n.item()),
+                               "timer_work_bytes": int(cl_each_work.numel()) * 4}
     nseg =[int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -658,6 +732,15 @@ def main():
                 "conv_old_born": 1 + 4 + 4 + 1 + 4 + 4 + 1})
     if "conv_flush_1m" in ops:
         alg["conv_flush_1m"], items["conv_flush_1m"] = 1 + 1 + 16 + 1 + 8, 1 << 20
+    # close, per row: state and the mark (rst_first or a byte) read by the count; with rows closing also read again
+    # by the row pass, the index cleared and written (8 B per row and more: >= 2 entries per row) and the keys read;
+    # the old path: the index cleared and written, state and the key read.  Per packet (conv_close_rst): conv_row
+    # and the rst_first gather -- left out of the row figures
+    for k, a_, rows_ in (("conv_close_none", 1 + 4, cl_cap), ("conv_close_rst", 2 * (1 + 4) + 8 + 4 + 4, cl_cap),
+                         ("conv_old_close", 8 + 4 + 1 + 4, cl_cap), ("conv_close_timer_1m", 1 + 1 + 2 * (1 + 1) + 8 + 4 + 4, 1 << 20),
+                         ("conv_old_close_1m", 8 + 4 + 1 + 4, 1 << 20)):
+        if k in ops:
+            alg[k], items[k] = a_, rows_
     # pick: id (BY_ID) and the avoid key read, conn written; the build reads state (and id) and writes cand, pos
     for k in ops:
         if k.startswith("conn_pick_build"):
@@ -722,6 +805,14 @@ def main():
             res["conv_create_none_over_conv_resolve_unknown"] = round(out["conv_create_none"]["ms"] / out["conv_resolve_unknown"]["ms"], 3)
         if "conv_create_born" in out and "conv_old_born" in out:
             res["conv_create_born_over_conv_old_born"] = round(out["conv_create_born"]["ms"] / out["conv_old_born"]["ms"], 3)
+        for k, y in (("conv_close_none", "conv_old_close"), ("conv_close_none", "conv_create_none"),
+                     ("conv_close_rst", "conv_old_close"), ("conv_close_timer_1m", "conv_old_close_1m")):
+            if k in out and y in out:
+                res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
+        if all(k in out for k in ("conv_close_timer_1m", "conv_flush_1m", "conv_old_close_1m")):
+            res["conv_flush_close_timer_1m_over_flush_old_close_1m"] = round(
+                (out["conv_flush_1m"]["ms"] + out["conv_close_timer_1m"]["ms"])
+                / (out["conv_flush_1m"]["ms"] + out["conv_old_close_1m"]["ms"]), 3)
         if "conv_flush_1m" in out and "keepalive_flush_1m" in out:
             res["conv_flush_1m_over_keepalive_flush_1m"] = round(out["conv_flush_1m"]["ms"] / out["keepalive_flush_1m"]["ms"], 3)
     picks = [k for k in out if k.startswith("conn_pick_")]
