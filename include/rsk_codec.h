@@ -643,8 +643,9 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
  * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
  * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
  * incremental insert or erase -- the conv table's rsk_conv_create_batch is the one insert there is, and
- * its rsk_conv_close_batch closes rows on the device by a rebuild of its own; this table's erase is clear LIVE
- * and rebuild); an index that was not rebuilt after such a change gives lookups of
+ * its rsk_conv_close_batch closes rows on the device by a rebuild of its own; this table's erase is
+ * rsk_conn_close_batch, which kills and removes rows on the device and keeps both indexes current, or clear LIVE
+ * and rebuild by the host); an index that was not rebuilt after such a change gives lookups of
  * the changed keys an unspecified row or RSK_CONN_NONE, never an access outside the table.  The other
  * columns need no rebuild.  The arrays are the caller's and do not move, so a call captured into a
  * hipGraph sees later row edits and rebuilds.
@@ -781,12 +782,13 @@ int rsk_conn_expand_host(const rsk_conn_table *tab, uint32_t n, const uint32_t *
  * reference's loop never ends (`continue` at :122 without a removal); here the packet gets NONE and is
  * counted.  The table is seen as the pick index was last built (a snapshot): which rows are dead is the
  * host's knowledge already, because it edits `state`.  The reference learns it inside the walk: a conn that a
- * NETCONN_RST of the same batch marked dead is still a candidate here until the host clears RSK_CONN_ALIVE
- * and rebuilds the pick index, where the reference's doSend would draw it, remove it and draw again.
+ * NETCONN_RST of the same batch marked dead is still a candidate here until rsk_conn_close_batch (behind the control
+ * pass in the chain) or the host clears RSK_CONN_ALIVE and brings the pick index up to date, where the reference's
+ * doSend would draw it, remove it and draw again.
  *
  * The pick index is a separate caller-owned buffer of rsk_conn_pick_bytes(capacity, flags) bytes, 16-B
- * aligned, rebuilt by the caller after any change to state or id (as rsk_conn_index_build after its
- * columns); avoid keys also go through tab->index.  A stale or never-built pick index gives an unspecified
+ * aligned, rebuilt by the caller after any host change to state or id (as rsk_conn_index_build after its
+ * columns; rsk_conn_close_batch keeps it current on the device when conns die); avoid keys also go through tab->index.  A stale or never-built pick index gives an unspecified
  * row of the table or RSK_CONN_NONE, never an access outside the table or the index.  It has one layout
  * on host and device: one built on either side and copied to the other is valid there. */
 uint64_t rsk_conn_pick_bytes(uint32_t capacity, uint32_t flags);      /* 0 for a bad capacity / flags */
@@ -809,7 +811,7 @@ typedef struct rsk_conn_pick_out {
     uint32_t *n_none;  /* [1] optional, written not accumulated: taken packets without a conn */
     uint8_t  *used;    /* [capacity] optional: used[conn[i]] = 1 */
 } rsk_conn_pick_out;
-/* No scratch and no host state: one memset node (n_none, when given) and one kernel, a linear chain that a
+/* No scratch and no host state: one one-thread kernel (n_none, when given) and one kernel, a linear chain that a
  * hipGraph captures without a reserve.  n == 0 zeroes a given n_none.  RSK_EINVAL: a NULL ctx, tab, pick,
  * in or out; a NULL conn with n > 0; id missing (in the table, or in `in` with n > 0) with BY_ID, or one
  * that is not 8-B aligned; avoid_key given on a table whose conn_key or index is NULL; unknown flags; a
@@ -829,9 +831,10 @@ int rsk_conn_pick_host(const rsk_conn_table *tab, const uint32_t *pick, uint32_t
  * body's key up in mConnMap and answer, report the conn or clear a pending request; a FIN / RST packet
  * (RSK_RECV_CLOSE) reaches IAppGroup::ProcessTcpFinOrRst (conn/IAppGroup.cpp:103-116).  The state they
  * touch is the table above, and NetConnKeepAlive::OnFlush (:110-145) is a pass over its rows.
- *   receive  parse_decode -> verify -> resolve -> rsk_control_batch -> rsk_conn_pick_batch (a conn per
- *            message, with the messages' id and avoid_key) -> expand -> send_seq -> rsk_encode_wire_batch
- *   timer    rsk_keepalive_flush -> the same message columns, and the rows that timed out
+ *   receive  parse_decode -> verify -> resolve -> rsk_control_batch -> rsk_conn_close_batch (the conns the batch
+ *            killed) -> rsk_conn_pick_batch (a conn per message, with the messages' id and avoid_key) -> expand ->
+ *            send_seq -> rsk_encode_wire_batch
+ *   timer    rsk_keepalive_flush -> the same message columns, and the rows that timed out -> rsk_conn_close_batch
  *
  * rsk_control_batch classifies packet i, reads the body of a control packet at
  * arena + base_off[i] + inner_off[i] + pay_off[i], and looks its key up by the resolve's rule: the LIVE
@@ -867,7 +870,8 @@ int rsk_conn_pick_host(const rsk_conn_table *tab, const uint32_t *pick, uint32_t
  * gone.  So in a batch that sends nothing (no message of this call, no other send of the group meanwhile)
  * every packet gets what the reference gives it; with sends, a packet at or before its row's rst_first
  * always does, and a later packet of that row does as long as no send has drawn the row.  rst_first is what
- * lets a caller redo the tail for the few rows concerned.  (tests/golden/control.npz holds the reference's
+ * lets a caller redo the tail for the few rows concerned, and what rsk_conn_close_batch takes to kill those rows
+ * before the answers are picked.  (tests/golden/control.npz holds the reference's
  * own walk, removals included.)
  *
  * Messages to send (rsk_ctl_msgs): an order-stable compacted list, in packet order, of
@@ -884,7 +888,8 @@ int rsk_conn_pick_host(const rsk_conn_table *tab, const uint32_t *pick, uint32_t
  * it reads conv).  Every array holds n entries and is optional; n_msg is required when any array is
  * given.  *n_msg and *n_ctl (the packets whose kind is not NONE) are written, not accumulated.
  *
- * Three launches on `stream`, a linear chain: per-tile counts, one block that scans them, and the pass
+ * Three launches on `stream` behind the fill of a given rst_first (a kernel, so that a captured chain replays
+ * it), a linear chain: per-tile counts, one block that scans them, and the pass
  * that classifies, gathers, probes and writes; no block waits on another.  Scratch: 8 B per 2048 packets
  * per stream, sized by rsk_reserve_stream, so a captured call replays.  n == 0 zeroes the given counts
  * and fills a given rst_first.  RSK_EINVAL: a NULL ctx, tab, in or out; a table a lookup cannot use (as
@@ -955,7 +960,8 @@ int rsk_control_batch(rsk_ctx *ctx, const rsk_conn_table *tab, uint32_t n, const
  * Both lists are in row order, their counts written, not accumulated.  A message has cmd
  * KEEP_ALIVE_REQ, body = the row's conn_key, id = the row's IdBuf (zeros for a table without an id
  * column), src = r, avoid_key 0, pay_off 8k, pay_len 8; the arrays hold `capacity` entries.  The table's
- * state stays read-only: the host clears ALIVE for the dead rows and rebuilds when it removes them.  No
+ * state stays read-only: rsk_conn_close_batch(close_rows = dead_rows, n_close = n_dead) kills (and removes) the
+ * dead rows on the device, or the host clears ALIVE for them and rebuilds when it removes them.  No
  * index is read.  The launches and the scratch are rsk_control_batch's (8 B per 1024 rows).
  * Against the reference's own OnFlush (tests/golden/control.npz) the requests, the timeouts and mReqMap
  * are the same per flush; the reference emits in mConns order (the keys' decimal strings), this pass in row
@@ -989,6 +995,90 @@ int rsk_control_host(const rsk_conn_table *tab, uint32_t n, const rsk_control_in
                      int nthreads);
 int rsk_keepalive_flush_host(const rsk_conn_table *tab, const rsk_keepalive *ka, const rsk_keepalive_out *out,
                              int nthreads);
+
+/* ---- conn close: fake-TCP conns killed and removed on the device table ------------------------------ */
+/* The two steps the reference takes when a conn dies, on the connection table, so that neither chain goes
+ * through the host:
+ *   receive  resolve -> rsk_control_batch (rst_first) -> rsk_conn_close_batch (column form) -> rsk_conn_pick_batch -> ...
+ *   timer    rsk_keepalive_flush (dead_rows, n_dead) -> rsk_conn_close_batch (list form) -> rsk_conn_pick_batch -> ...
+ * KILL.  INetConn::NotifyErr sets mAlive = false (conn/INetConn.cpp:49-52; from ConnReset::OnRecvNetConnRst,
+ * callbacks/ConnReset.cpp:79-90, IAppGroup::ProcessTcpFinOrRst, and the keepalive timeout,
+ * callbacks/NetConnKeepAlive.cpp:110-145).  The conn stays in mConnMap: lookups still find it.
+ * REMOVE.  INetGroup::childConnErrCb -> RemoveConn erases it from mConns and mConnMap
+ * (conn/INetGroup.cpp:94-101, :138-146), reached from IGroup::Flush for every conn that is not alive
+ * (conn/IGroup.cpp:81-111) and from doSend for the dead conn it drew (conn/INetGroup.cpp:129-130).
+ *
+ * Marks.  At most one of close_rows and rst_first is given; with neither, RSK_CONN_CLOSE_SWEEP is required (that
+ * call is IGroup::Flush alone).  List form: the marked rows are the first min(*n_close, m_max) entries of
+ * close_rows (*n_close is a device word the host need not read); entries >= capacity, entries naming a row that
+ * is not LIVE and repeats mark nothing extra.  Column form: row r is marked iff rst_first[r] != 0xFFFFFFFF.  No
+ * packet column is read or written in either form: the call takes no n.
+ * Kill.  A marked row that is LIVE loses RSK_CONN_ALIVE; it is counted in *n_marked and listed in marked_rows
+ * iff it had the bit.
+ * Remove.  With RSK_CONN_CLOSE_REMOVE every marked LIVE row is removed; with RSK_CONN_CLOSE_SWEEP also every
+ * LIVE row without ALIVE, the rows killed by an earlier call or by the host included.  A removed row loses
+ * LIVE, ALIVE and RSK_CONN_NEW; its other state bits and every other column stay bytewise untouched.  It is
+ * listed once in closed_rows (the host closes the socket, and on a client redials).  ka_tries of a removed row
+ * is left to the next rsk_keepalive_flush, whose step 1 is removeInvalidRequest.
+ * Both lists are in row order; their counts are written, not accumulated, and nothing behind them is written.
+ * State is written through rows->state, which must alias tab->state.
+ * Conn index.  After a call that removed something every lookup gives what rsk_conn_index_build over the new
+ * state gives: the index is rebuilt over the rows that stay (open addressing without tombstones has no erase
+ * in place).  After a call that removed nothing no byte of tab->index is written: a kill alone never touches
+ * it, as the reference's lookups still find a dead conn.
+ * Pick index (out->pick, optional).  Precondition: it was current for the state the call found (built by
+ * rsk_conn_pick_build, or kept by earlier calls of this function).  Afterwards every rsk_conn_pick_batch result
+ * equals the result on an index freshly built over the new state, for any id, draw and avoid key, and so do
+ * the header words and pick_counts (written by every call that has `pick`; not looked at without it).  The bytes may differ: a group that lost every
+ * candidate keeps its entry, with an offset that the pick's bounds turn into NONE, and `lead` keeps what the
+ * build left.  When no row lost ALIVE or LIVE no byte of it is written.  The update is a parallel, order-stable
+ * compaction of the candidates (a close only takes candidates away).  Every value read from the pick index is
+ * bounded before it is used as an offset: a stale or garbage index gives an unspecified index again, and never
+ * an access outside the index, work or the table.
+ * work: rsk_conn_close_bytes(capacity, table flags) bytes, 16-B aligned, caller-owned, contents do not matter;
+ * one per stream that runs the call.
+ * Launches: a linear chain of kernels on `stream` and no memset node (list form: clear and scatter the marks;
+ * per 1024-row tile the counts of the rows that lose ALIVE, of those that lose LIVE and of the candidates
+ * that stay; two one-block scans of the tile counts; one launch for the two lists, the clear of the conn index
+ * and the scatter of the staying candidates into work; one for the rows' state and their insertion, the copy
+ * back into the pick index and its group entries).  The last two leave at once when no row lost ALIVE or LIVE.
+ * No launch walks the rows on one block, no block waits on another, nothing spins, no block reads a region of
+ * an index that another block of the same launch writes, and every probe loop is bounded by its table's size.
+ * The per-tile counts live in the control path's per-stream scratch (rsk_reserve_stream before a capture); the
+ * chain captures into a hipGraph and replays on edited columns.  A row's state byte is written by the one lane
+ * that owns the row.
+ * RSK_EINVAL: a NULL ctx, tab, rows, in, out or work; a table a lookup cannot use, or without state;
+ * rows->state != tab->state; both mark sources given, or none without SWEEP; unknown flags; list form without
+ * n_close; marked_rows without n_marked, closed_rows without n_closed; a work, index or pick that is not 16-B
+ * aligned; an id column (BY_ID) that is not 8-B aligned; a capacity outside [1, RSK_CONN_MAX_ROWS]. */
+#define RSK_CONN_CLOSE_REMOVE 0x1u  /* the marked rows are also removed (RemoveConn of named conns)   */
+#define RSK_CONN_CLOSE_SWEEP  0x2u  /* every LIVE row without ALIVE is removed (IGroup::Flush)        */
+uint64_t rsk_conn_close_bytes(uint32_t capacity, uint32_t table_flags); /* 0 for a bad capacity / flags */
+
+typedef struct rsk_conn_rows { uint8_t *state; } rsk_conn_rows;   /* writable alias of tab->state */
+
+typedef struct rsk_conn_close_in {
+    const uint32_t *close_rows; /* [m_max] list form: e.g. rsk_keepalive_flush's dead_rows            */
+    const uint32_t *n_close;    /* [1] list form: device word, e.g. its n_dead                        */
+    uint32_t m_max;
+    const uint32_t *rst_first;  /* [capacity] column form: rsk_control_batch's, as it left it         */
+    void *work;                 /* rsk_conn_close_bytes(...) bytes, 16-B aligned, caller-owned        */
+    uint32_t flags;             /* RSK_CONN_CLOSE_*                                                    */
+} rsk_conn_close_in;
+
+typedef struct rsk_conn_close_out {
+    uint32_t *marked_rows, *n_marked;  /* rows that lost ALIVE in this call, row order; count written */
+    uint32_t *closed_rows, *n_closed;  /* rows that lost LIVE in this call, row order; count written  */
+    uint32_t *pick;                    /* optional: the table's pick index, kept current              */
+    uint32_t *pick_counts;             /* [2] optional, as rsk_conn_pick_build's counts               */
+} rsk_conn_close_out;
+
+int rsk_conn_close_batch(rsk_ctx *ctx, const rsk_conn_table *tab, const rsk_conn_rows *rows,
+                         const rsk_conn_close_in *in, const rsk_conn_close_out *out, void *stream);
+/* The twin: host pointers, the same rules, outputs, work buffer and index layouts (a table closed on one side
+ * and copied to the other is valid there); sequential on the caller's thread; the IdBuf column at any alignment. */
+int rsk_conn_close_host(const rsk_conn_table *tab, const rsk_conn_rows *rows, const rsk_conn_close_in *in,
+                        const rsk_conn_close_out *out, int nthreads);
 
 /* ---- conv table: a DATA packet's conv, the convs' activity counts and their flush ------------------ */
 /* The reference's last lookup before a payload reaches anybody: on a server SubGroup::OnRecv looks

@@ -54,6 +54,7 @@ KA_REQUEST_DELAY_MS = 15000
 KA_MAX_RETRY = 3
 CONV_BY_DST, CONV_BY_ID = 0x1, 0x2
 CONV_CLOSE_HOLD = 0x1
+CONN_CLOSE_REMOVE, CONN_CLOSE_SWEEP = 0x1, 0x2
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -198,6 +199,20 @@ class Keepalive(ctypes.Structure):
 
 class KeepaliveOut(ctypes.Structure):
     _fields_ = [("msgs", CtlMsgs), ("dead_rows", _vp), ("n_dead", _vp)]
+
+
+class ConnRows(ctypes.Structure):
+    _fields_ = [("state", _vp)]
+
+
+class ConnCloseIn(ctypes.Structure):
+    _fields_ = [("close_rows", _vp), ("n_close", _vp), ("m_max", ctypes.c_uint32), ("rst_first", _vp), ("work", _vp),
+                ("flags", ctypes.c_uint32)]
+
+
+class ConnCloseOut(ctypes.Structure):
+    _fields_ = [("marked_rows", _vp), ("n_marked", _vp), ("closed_rows", _vp), ("n_closed", _vp), ("pick", _vp),
+                ("pick_counts", _vp)]
 
 
 class ConvTable(ctypes.Structure):
@@ -355,6 +370,13 @@ SIGNATURES = [
     ("rsk_conv_create_host", ctypes.c_int,
      [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCreateIn),
       ctypes.POINTER(ConvCreateOut), ctypes.c_int]),
+    ("rsk_conn_close_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_conn_close_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.POINTER(ConnRows), ctypes.POINTER(ConnCloseIn),
+      ctypes.POINTER(ConnCloseOut), _vp]),
+    ("rsk_conn_close_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.POINTER(ConnRows), ctypes.POINTER(ConnCloseIn), ctypes.POINTER(ConnCloseOut),
+      ctypes.c_int]),
     ("rsk_conv_close_bytes", ctypes.c_uint64, [ctypes.c_uint32]),
     ("rsk_conv_close_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCloseIn),

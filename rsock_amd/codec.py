@@ -349,6 +349,18 @@ class ConnTable:
         return ConnTable(self.capacity, self.by_id, *[mv(getattr(self, name)) for name, _, _ in _CONN_COLUMNS],
                          mv(self.index), mv(self.pick))
 
+    def abi_rows(self) -> _abi.ConnRows:
+        """The writable alias of state that conn_close_batch / conn_close_host take."""
+        return _abi.ConnRows(_ptr(self.state))
+
+    def close_work(self) -> torch.Tensor:
+        """The work buffer of conn_close_batch / conn_close_host (rsk_conn_close_bytes), on the table's device;
+        one per stream that runs the call."""
+        nbytes = lib().rsk_conn_close_bytes(self.capacity, self.flags)
+        if nbytes == 0:
+            raise RskError(f"rsk_conn_close_bytes: bad capacity {self.capacity}")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
     def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
         """rsk_conn_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
         table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
@@ -442,6 +454,29 @@ def _addr(a) -> int | None:
     if a is None:
         return None
     return a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+
+
+def _conn_close_structs(tab, close_rows, n_close, m_max, rst_first, work, remove, sweep, marked_rows, n_marked,
+                        closed_rows, n_closed, pick, pick_counts):
+    if m_max is None:
+        m_max = 0 if close_rows is None else len(close_rows)
+    flags = (_abi.CONN_CLOSE_REMOVE if remove else 0) | (_abi.CONN_CLOSE_SWEEP if sweep else 0)
+    cin = _abi.ConnCloseIn(_addr(close_rows), _addr(n_close), int(m_max), _addr(rst_first), _addr(work), flags)
+    cout = _abi.ConnCloseOut(_addr(marked_rows), _addr(n_marked), _addr(closed_rows), _addr(n_closed),
+                             _addr(tab.pick) if pick else None, _addr(pick_counts))
+    return cin, cout
+
+
+def conn_close_host(tab: ConnTable, work, close_rows=None, n_close=None, m_max: int | None = None, rst_first=None,
+                    remove: bool = False, sweep: bool = False, marked_rows=None, n_marked=None, closed_rows=None,
+                    n_closed=None, pick: bool = False, pick_counts=None, nthreads: int = 1) -> None:
+    """rsk_conn_close_host on a "cpu" ConnTable (no GPU); the arguments of Codec.conn_close_batch."""
+    cin, cout = _conn_close_structs(tab, close_rows, n_close, m_max, rst_first, work, remove, sweep, marked_rows,
+                                    n_marked, closed_rows, n_closed, pick, pick_counts)
+    rc = lib().rsk_conn_close_host(ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()), ctypes.byref(cin),
+                                   ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conn_close_host failed: rc={rc}")
 
 
 _MSG_COLUMNS = (("msg_cmd", torch.uint8, 1), ("msg_body", torch.int64, 1), ("msg_id", torch.uint8, 8),
@@ -1138,6 +1173,22 @@ class Codec:
         _check(lib().rsk_conv_create_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()),
                                            conv_row.numel(), ctypes.byref(cin), ctypes.byref(cout), _stream(stream)),
                "rsk_conv_create_batch")
+
+    def conn_close_batch(self, tab: "ConnTable", work, close_rows=None, n_close=None, m_max: int | None = None,
+                         rst_first=None, remove: bool = False, sweep: bool = False, marked_rows=None, n_marked=None,
+                         closed_rows=None, n_closed=None, pick: bool = False, pick_counts=None, stream=None) -> None:
+        """INetConn::NotifyErr and INetGroup::RemoveConn on the device table (rsk_conn_close_batch).  The marks are
+        a list (close_rows / n_close, e.g. keepalive_flush's dead_rows / n_dead; m_max defaults to
+        len(close_rows)), a column (rst_first, control_batch's) or none (sweep alone).  A marked LIVE row loses
+        CONN_ALIVE (marked_rows / n_marked); with remove it also leaves the table, with sweep every LIVE row
+        without ALIVE does (closed_rows / n_closed), and the conn index is rebuilt over the rows that stay.
+        pick=True keeps tab.pick current (it must be current for the state the call finds); pick_counts [2] as
+        conn_pick_build's counts.  work = tab.close_work(), one per stream.  Captures into a graph after
+        reserve(stream=...)."""
+        cin, cout = _conn_close_structs(tab, close_rows, n_close, m_max, rst_first, work, remove, sweep, marked_rows,
+                                        n_marked, closed_rows, n_closed, pick, pick_counts)
+        _check(lib().rsk_conn_close_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()),
+                                          ctypes.byref(cin), ctypes.byref(cout), _stream(stream)), "rsk_conn_close_batch")
 
     def conv_close_batch(self, tab: "ConvTable", close_rows=None, n_close=None, m_max: int | None = None, work=None,
                          rst_first=None, ctl_kind=None, conv_row=None, unknown=None, n_unknown=None, hold: bool = False,

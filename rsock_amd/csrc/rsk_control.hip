@@ -28,7 +28,6 @@ using rsk::funnel;
 using rsk::gptr;
 using rsk::k_tile_scan;
 using rsk::kScanBlock;
-using rsk::memset_async;
 using rsk::misaligned8;
 using rsk::msg_out;
 using rsk::MsgOut;
@@ -337,7 +336,8 @@ extern "C" int rsk_control_batch(rsk_ctx *c, const rsk_conn_table *t, uint32_t n
     if (!g.ok) return RSK_EDEVICE;
     hipStream_t s = (hipStream_t)stream;
     int r;
-    if (out->rst_first && (r = memset_async(out->rst_first, 0xFF, 4ull * t->capacity, s))) return r;
+    // a kernel, not a memset node: the captured chain control -> conn_close reads the column again (rsk_tile_dev.h)
+    if (out->rst_first && (r = rsk::fill_words_async(out->rst_first, t->capacity, 0xFFFFFFFFu, s))) return r;
     if (n == 0) {
         if ((r = rsk::zero_word(out->msgs.n_msg, s))) return r;
         return rsk::zero_word(out->n_ctl, s);

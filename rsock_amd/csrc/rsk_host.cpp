@@ -3,7 +3,7 @@
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
 // (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
 // (rsk_conn_*_host) with its send pick (rsk_conn_pick_*host), its control packets and keepalive timer (rsk_control_host,
-// rsk_keepalive_flush_host) and of the conv table (rsk_conv_*_host); the single-frame slot staging, the capture filter's text form and the connection
+// rsk_keepalive_flush_host), its close (rsk_conn_close_host) and of the conv table (rsk_conv_*_host); the single-frame slot staging, the capture filter's text form and the connection
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
@@ -576,6 +576,116 @@ extern "C" int rsk_keepalive_flush_host(const rsk_conn_table *t, const rsk_keepa
     }
     if (out->msgs.n_msg) *out->msgs.n_msg = n_msg;
     if (out->n_dead) *out->n_dead = n_dead;
+    return RSK_OK;
+}
+
+// ---- conn close (rsk_conn_close_batch): the host twin; the pick update's layout and arithmetic in rsk_pick.h ----
+extern "C" uint64_t rsk_conn_close_bytes(uint32_t capacity, uint32_t flags) {
+    if ((flags & ~RSK_CONN_BY_ID) || capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    return 4ull * rsk::close_layout(capacity, (flags & RSK_CONN_BY_ID) != 0).words;
+}
+
+// The marks (list form: in `work`, as on the device), the two lists and the pick index from the state the call
+// found, then the rows' state, and the conn index over the rows that stay when one was removed.
+extern "C" int rsk_conn_close_host(const rsk_conn_table *t, const rsk_conn_rows *rows, const rsk_conn_close_in *in,
+                                   const rsk_conn_close_out *out, int /*nthreads*/) {
+    constexpr uint8_t kUp = RSK_CONN_LIVE | RSK_CONN_ALIVE, kGone = RSK_CONN_LIVE | RSK_CONN_ALIVE | RSK_CONN_NEW;
+    if (!rows || !in || !out || !conn_tab_lookup_ok(t) || !t->state) return RSK_EINVAL;
+    if (rows->state != t->state || !in->work) return RSK_EINVAL;
+    const bool list = in->close_rows != nullptr, col = in->rst_first != nullptr;
+    if ((in->flags & ~(RSK_CONN_CLOSE_REMOVE | RSK_CONN_CLOSE_SWEEP)) || (list && col) ||
+        (!list && !col && !(in->flags & RSK_CONN_CLOSE_SWEEP)))
+        return RSK_EINVAL;
+    if (list && !in->n_close) return RSK_EINVAL;
+    if ((out->marked_rows && !out->n_marked) || (out->closed_rows && !out->n_closed)) return RSK_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(t->index) | reinterpret_cast<uintptr_t>(in->work) | reinterpret_cast<uintptr_t>(out->pick)) & 15u)
+        return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    const bool remove = (in->flags & RSK_CONN_CLOSE_REMOVE) != 0, sweep = (in->flags & RSK_CONN_CLOSE_SWEEP) != 0;
+    const uint32_t cap = t->capacity, c4 = (cap + 3u) & ~3u;
+    const rsk::CloseLayout wl = rsk::close_layout(cap, by_id);
+    uint32_t *work = static_cast<uint32_t *>(in->work);
+    const uint8_t *mark = list ? static_cast<const uint8_t *>(in->work) : nullptr;
+    if (list) {
+        uint8_t *mk = static_cast<uint8_t *>(in->work);
+        std::memset(mk, 0, 4ull * wl.k);
+        const uint32_t m = *in->n_close < in->m_max ? *in->n_close : in->m_max;
+        for (uint32_t j = 0; j < m; ++j)
+            if (in->close_rows[j] < cap) mk[in->close_rows[j]] = 1;
+    }
+    auto marked = [&](uint32_t r) { return mark ? mark[r] != 0 : col ? in->rst_first[r] != 0xFFFFFFFFu : false; };
+    auto next_state = [&](uint32_t r) {
+        uint8_t st = rows->state[r];
+        if (!(st & RSK_CONN_LIVE)) return st;
+        const bool m = marked(r);
+        if (m) st = (uint8_t)(st & ~RSK_CONN_ALIVE);
+        if ((remove && m) || (sweep && !(st & RSK_CONN_ALIVE))) st = (uint8_t)(st & ~kGone);
+        return st;
+    };
+    uint32_t n_marked = 0, n_closed = 0;
+    for (uint32_t r = 0; r < cap; ++r) {
+        const uint8_t d = (uint8_t)(rows->state[r] ^ next_state(r));
+        if (d & RSK_CONN_ALIVE) {
+            if (out->marked_rows) out->marked_rows[n_marked] = r;
+            ++n_marked;
+        }
+        if (d & RSK_CONN_LIVE) {
+            if (out->closed_rows) out->closed_rows[n_closed] = r;
+            ++n_closed;
+        }
+    }
+    if (out->pick && n_marked) {  // a row lost ALIVE: the candidates compacted in place (a new position is no later)
+        uint32_t *pick = out->pick;
+        const rsk::PickLayout pl = rsk::pick_layout(cap, by_id);
+        const uint32_t tot0 = pick[0] < cap ? pick[0] : cap, kt = wl.tiles * rsk::kPickTile;
+        uint32_t *K = work + wl.k;
+        uint32_t total = 0;
+        for (uint32_t j = 0; j < kt; ++j) {
+            K[j] = total;
+            if (j >= tot0) continue;
+            const uint32_t r = pick[pl.cand + j];
+            if (r >= cap) continue;
+            if ((rows->state[r] & kUp) != kUp || marked(r)) {
+                pick[pl.pos + r] = rsk::kConnEmpty;
+                continue;
+            }
+            const uint32_t p = pick[pl.pos + r], o = p <= j ? j - p : rsk::kConnEmpty;  // the group's old offset
+            pick[pl.cand + total] = r;
+            pick[pl.pos + r] = !by_id ? total : o < cap && K[o] <= total ? total - K[o] : rsk::kConnEmpty;
+            ++total;
+        }
+        for (uint32_t j = total; j < c4; ++j) pick[pl.cand + j] = rsk::kConnEmpty;
+        auto k_at = [&](uint32_t j) { return j < kt ? K[j] : total; };
+        uint32_t groups = pick[1];
+        if (!by_id) groups = total != 0u;
+        for (uint32_t s = 0; by_id && s < rsk::conn_slots(cap); ++s) {
+            uint32_t *g = pick + pl.group + 4ull * s;  // {id lo, id hi, off, cnt}
+            if (g[3] == 0u || g[2] >= cap || g[3] > cap - g[2]) continue;  // free, emptied before, or garbage
+            const uint32_t k0 = k_at(g[2]), k1 = k_at(g[2] + g[3]);
+            if (k1 > k0) {
+                g[2] = k0;
+                g[3] = k1 - k0;
+            } else {
+                g[2] = rsk::kPickGoneOff;
+                g[3] = rsk::kPickGoneCnt;
+                --groups;
+            }
+        }
+        pick[0] = total;
+        pick[1] = groups;
+    }
+    if (out->pick && out->pick_counts) {
+        out->pick_counts[0] = out->pick[1];
+        out->pick_counts[1] = out->pick[0];
+    }
+    if (n_marked || n_closed)
+        for (uint32_t r = 0; r < cap; ++r) {
+            const uint8_t ns = next_state(r);
+            if (ns != rows->state[r]) rows->state[r] = ns;
+        }
+    if (n_closed) index_build_host(HostConnTab{t}, t->index, t->state, cap, by_id, nullptr);
+    if (out->n_marked) *out->n_marked = n_marked;
+    if (out->n_closed) *out->n_closed = n_closed;
     return RSK_OK;
 }
 

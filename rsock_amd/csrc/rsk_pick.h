@@ -101,4 +101,37 @@ RSK_CONN_HD uint32_t pick_row(const P &p, uint32_t capacity, uint32_t off, uint3
     return r < capacity ? r : kConnEmpty;
 }
 
+// ---- rsk_conn_close_batch's work buffer and its update of the pick index (rsk_conn_close.hip, rsk_host.cpp) ----
+// A close only takes candidates away, and a group's candidates are contiguous in cand: the new cand is the old
+// one compacted order-stably over the entries whose row stays LIVE|ALIVE.  With K[j] = the kept entries before
+// entry j, entry j moves to K[j], a group {off, cnt} becomes {K[off], K[off + cnt] - K[off]}, and a row's new
+// position is K[j] - K[its group's off], where the group's old offset is j - (the row's old position): no
+// group is looked up.  A group that lost every candidate keeps its entry as kPickGone, which pick_group's
+// bounds turn into NONE: a count of 0 would free the entry and cut the probe chains of other ids.  lead is
+// left as the build made it (only the build reads it, and it writes it first).
+// work, 16-B aligned, in 32-bit words behind the marks:
+//   [0, C16) bytes  mark: one byte per row (list form), C16 = C rounded up to a multiple of 16
+//   K        [T]    T = the capacity rounded up to a multiple of kPickTile; all of it is written by a call
+//                   that changes the pick index
+//   cand     [C4]   the kept rows at their new positions
+//   goff     [C4]   BY_ID only: per new position, the old offset of the entry's group (kConnEmpty: none)
+constexpr uint32_t kPickTile = 1024u;                        // entries of cand per tile of the update
+constexpr uint32_t kPickGoneOff = 0xFFFFFFFFu, kPickGoneCnt = 1u;  // {off, cnt} of a group without candidates
+
+struct CloseLayout {
+    uint32_t k, cand, goff, words;  // word offsets into work, and the total
+    uint32_t tiles;                 // tiles of kPickTile rows or entries
+};
+
+RSK_CONN_HD CloseLayout close_layout(uint32_t capacity, bool by_id) {
+    const uint32_t c4 = (capacity + 3u) & ~3u, c16 = (capacity + 15u) & ~15u;
+    CloseLayout l;
+    l.tiles = (capacity + kPickTile - 1u) / kPickTile;
+    l.k = c16 / 4u;
+    l.cand = l.k + l.tiles * kPickTile;
+    l.goff = l.cand + c4;
+    l.words = l.goff + (by_id ? c4 : 0u);
+    return l;
+}
+
 }  // namespace rsk

@@ -134,6 +134,8 @@ __global__ __launch_bounds__(kBlock) void k_conn_pick(PickArgs a) {
     }
 }
 
+__global__ void k_pick_zero(uint32_t *word) { *gptr(word) = 0u; }
+
 // ---- the build ---------------------------------------------------------------------------------------
 
 // The rows as k_index_build keys them for the groups: the IdBuf alone.
@@ -343,7 +345,12 @@ extern "C" int rsk_conn_pick_batch(rsk_ctx *c, const rsk_conn_table *t, const ui
     rsk::DeviceGuard g(c->device);
     if (!g.ok) return RSK_EDEVICE;
     hipStream_t s = (hipStream_t)stream;
-    if (int r = rsk::zero_word(out->n_none, s)) return r;
+    // a kernel, not a memset node: behind rsk_conn_close_batch the call is part of captured chains, and replays of
+    // a graph were seen to run a memset node with a stale pattern (rsk_tile_dev.h's k_fill_words)
+    if (out->n_none) {
+        hipLaunchKernelGGL(k_pick_zero, dim3(1), dim3(1), 0, s, out->n_none);
+        if (int r = rsk::launch_check("k_pick_zero")) return r;
+    }
     if (n == 0) return RSK_OK;
     PickArgs a;
     a.t = rsk::dev_tab(t);

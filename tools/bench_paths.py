@@ -14,6 +14,9 @@ over 2^20 rows, each with and without the
 cur_in counts; IGroup::Flush over 2^20 rows) /
 conv_close_none / conv_close_rst / conv_close_timer_1m / conv_old_close / conv_old_close_1m (rsk_conv_close_batch
 with no reset hitting, with 1 % of the convs reset, behind the flush of 2^20 rows, and the index rebuild it replaces) /
+conn_close_none / conn_close_rst / conn_close_timer_1m (+ _by_id) / conn_old_* (rsk_conn_close_batch with the pick
+index kept current: nothing marked, 1 % of the batch's conns reset and removed, a fifth of 2^20 rows timed out and
+removed, and the rsk_conn_index_build + rsk_conn_pick_build they replace) /
 conv_resolve_unknown / conv_create_none / conv_create_born / conv_old_born (rsk_conv_create_batch on the one-conv-
 per-connection column: no packet unknown beside the resolve alone, every conv born in the call on an empty table,
 and the demux + index build + second resolve that the same outcome takes without the call) /
@@ -649,6 +652,64 @@ def main():
     conv_rows["conv_close"] = {"capacity": cl_cap, "convs_reset": int(cl_reset_rows.numel()), "packets_reopened": cl_tail,
                                "timer_rows": 1 << 20, "timer_closed": int(cl_each_n.item()),
                                "timer_work_bytes": int(cl_each_work.numel()) * 4}
+    # conn close (rsk_conn_close_batch): conns killed and removed on the device table, the pick index kept current
+    #   conn_close_none            column form on the table of the batch's own conns, nothing marked, with pick: what
+    #                              keeping the call in the chain costs (5 launches)
+    #   conn_close_rst             the same table, 1 % of the rows marked, REMOVE and pick
+    #   conn_close_timer_1m(_by_id) 2^20 rows (one group / groups of 10), a fifth marked by a list, REMOVE and pick
+    #   conn_old_*                 the device share of the old path for the same outcome on the same tables:
+    #                              rsk_conn_index_build + rsk_conn_pick_build; the host's round trip and state edit
+    #                              are left out, which favours the old path
+    # state, index and pick are restored outside the timed span.
+    def cc_twin(t):
+        t = dataclasses.replace(t, state=t.state.clone(), index=t.index.clone(), pick=t.pick.clone())
+        t.rebuild(cx, stream=s)
+        t.rebuild_pick(cx, stream=s)
+        torch.cuda.synchronize()
+        return t, (t.state.clone(), t.index.clone(), t.pick.clone())
+
+    def cc_restore(t, saved):
+        return lambda: (t.state.copy_(saved[0]), t.index.copy_(saved[1]), t.pick.copy_(saved[2]))
+
+    cc_out = {k: torch.empty(1 << 20, dtype=torch.int32, device=dev) for k in ("marked_rows", "closed_rows")}
+    cc_cnt = torch.zeros(6, dtype=torch.int32, device=dev)  # n_marked, n_closed, pick_counts[2]
+    cc_kw = dict(marked_rows=cc_out["marked_rows"], n_marked=cc_cnt[0:1], closed_rows=cc_out["closed_rows"],
+                 n_closed=cc_cnt[1:2], pick=True, pick_counts=cc_cnt[2:4], stream=s)
+    cc_own, cc_own0 = cc_twin(tab_own)
+    cc_work = cc_own.close_work()
+    cc_no_rst = torch.full((cc_own.capacity,), -1, dtype=torch.int32, device=dev)
+    cc_rst = cc_no_rst.clone()
+    cc_rst[::100] = 0
+    ops["conn_close_none"] = lambda: cx.conn_close_batch(cc_own, cc_work, rst_first=cc_no_rst, **cc_kw)
+    ops["conn_close_rst"] = lambda: cx.conn_close_batch(cc_own, cc_work, rst_first=cc_rst, remove=True, **cc_kw)
+    prep["conn_close_rst"] = cc_restore(cc_own, cc_own0)
+    ops["conn_old_none"] = ops["conn_old_rst"] = lambda: (cx.conn_index_build(cc_own, stream=s),
+                                                          cx.conn_pick_build(cc_own, stream=s))
+    cc_dead = torch.arange(0, 1 << 20, 5, device=dev, dtype=torch.int32)
+    cc_nd = torch.tensor([cc_dead.numel()], dtype=torch.int32, device=dev)
+    cc_rows = {"conn_close_none": {"rows": cc_own.capacity, "marked": 0},
+               "conn_close_rst": {"rows": cc_own.capacity, "marked": int((cc_rst != -1).sum().item())}}
+    for name, src_tab in (("timer_1m", pk_1m), ("timer_1m_by_id", pk_1mg)):
+        t1, saved1 = cc_twin(src_tab)
+        w1 = t1.close_work()
+        ops["conn_close_" + name] = lambda t1=t1, w1=w1: cx.conn_close_batch(t1, w1, close_rows=cc_dead, n_close=cc_nd,
+                                                                             remove=True, **cc_kw)
+        prep["conn_close_" + name] = cc_restore(t1, saved1)
+        ops["conn_old_" + name] = lambda t1=t1: (cx.conn_index_build(t1, stream=s), cx.conn_pick_build(t1, stream=s))
+        ops["conn_close_" + name]()
+        torch.cuda.synchronize()
+        assert cc_cnt.tolist()[:4] == [cc_dead.numel(), cc_dead.numel(), (1 << 20) // 10 if name.endswith("by_id") else 1,
+                                       (1 << 20) - cc_dead.numel()], (name, cc_cnt.tolist())
+        assert int((t1.state == 3).sum().item()) == (1 << 20) - cc_dead.numel()
+        prep["conn_close_" + name]()
+        cc_rows["conn_close_" + name] = {"rows": 1 << 20, "marked": int(cc_dead.numel()), "work_bytes": int(w1.numel()) * 4}
+    ops["conn_close_none"]()
+    torch.cuda.synchronize()
+    assert cc_cnt.tolist()[:2] == [0, 0] and torch.equal(cc_own.index, cc_own0[1]) and torch.equal(cc_own.pick, cc_own0[2])
+    ops["conn_close_rst"]()
+    torch.cuda.synchronize()
+    assert cc_cnt.tolist()[:2] == [cc_rows["conn_close_rst"]["marked"]] * 2
+    prep["conn_close_rst"]()
     nseg =[int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -741,6 +802,10 @@ def main():
                          ("conv_old_close_1m", 8 + 4 + 1 + 4, 1 << 20)):
         if k in ops:
             alg[k], items[k] = a_, rows_
+    # conn close / the old path, per row: state and the mark read (left as the figure for every row of the family)
+    for k in ops:
+        if k.startswith(("conn_close_", "conn_old_")):
+            alg[k], items[k] = 1 + 4, (1 << 20) if "_1m" in k else cc_own.capacity
     # pick: id (BY_ID) and the avoid key read, conn written; the build reads state (and id) and writes cand, pos
     for k in ops:
         if k.startswith("conn_pick_build"):
@@ -815,6 +880,14 @@ def main():
                 / (out["conv_flush_1m"]["ms"] + out["conv_old_close_1m"]["ms"]), 3)
         if "conv_flush_1m" in out and "keepalive_flush_1m" in out:
             res["conv_flush_1m_over_keepalive_flush_1m"] = round(out["conv_flush_1m"]["ms"] / out["keepalive_flush_1m"]["ms"], 3)
+    if any(k.startswith("conn_close_") for k in out):
+        res["conn_close_rows"] = {k: v for k, v in cc_rows.items() if k in out}
+        for k in [k for k in out if k.startswith("conn_close_")]:
+            y = "conn_old_" + k[len("conn_close_"):]
+            if y in out:
+                res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
+        if "conn_close_none" in out and "conv_close_none" in out:
+            res["conn_close_none_over_conv_close_none"] = round(out["conn_close_none"]["ms"] / out["conv_close_none"]["ms"], 3)
     picks = [k for k in out if k.startswith("conn_pick_")]
     if picks:
         res["conn_pick_rows"] = {"client": 10, "server": [64, 10], "own_one": n_own, "own_groups": [g_own, 10],
