@@ -45,6 +45,10 @@
  *   rsk_conn_pick_batch   <- INetGroup::doSend's pick of an alive conn per outgoing packet, the conn to
  *                            reset excepted (conn/INetGroup.cpp:111-135)
  *   rsk_conn_table        <- INetGroup's mConnMap and the TcpInfo mInfo of each FakeTcp in it
+ *   rsk_conn_create_batch <- INetGroup::Input's miss path (conn/INetGroup.cpp:57-83): SNetGroup::CreateNetConn
+ *                            (server/SNetGroup.cpp:20-46), ServerNetManager::GetTcp
+ *                            (server/ServerNetManager.cpp:52-75), FakeTcp::Init and AddNetConn; a client's
+ *                            AddNetConn behind DialTcpSync / DialTcpAsync (client/CNetGroup.cpp:11-13)
  *   rsk_control_batch     <- IAppGroup::Input's control branches (conn/IAppGroup.cpp:76-96), ConnReset::Input
  *                            (callbacks/ConnReset.cpp:43-90), NetConnKeepAlive::Input
  *                            (callbacks/NetConnKeepAlive.cpp:37-98), IAppGroup::ProcessTcpFinOrRst
@@ -641,11 +645,10 @@ int rsk_verify_wire_host(uint32_t n, const rsk_verify_in *in, int datalink, cons
  *   send     rsk_conn_pick_batch -> conn[i]; rsk_conn_expand_batch(conn) -> src, dst, sp, dp, ack, flag
  *            (rsk_wire_in) and conn_key, id (rsk_encode_in); seq and ip_id from rsk_tcp_send_seq_batch(conn, status, capacity, tab.seq, ...)
  * The host edits rows with ordinary copies on its streams and calls rsk_conn_index_build after any
- * change to state, conn_key or id (set-up and tear-down are rare: one rebuild over the capacity, no
- * incremental insert or erase -- the conv table's rsk_conv_create_batch is the one insert there is, and
- * its rsk_conv_close_batch closes rows on the device by a rebuild of its own; this table's erase is
- * rsk_conn_close_batch, which kills and removes rows on the device and keeps both indexes current, or clear LIVE
- * and rebuild by the host); an index that was not rebuilt after such a change gives lookups of
+ * change to state, conn_key or id (one rebuild over the capacity; this table's insert is rsk_conn_create_batch,
+ * which makes the conns of a receive batch or a client's dials on the device, its erase rsk_conn_close_batch,
+ * which kills and removes rows there; both keep both indexes current; the conv table has
+ * rsk_conv_create_batch and rsk_conv_close_batch); an index that was not rebuilt after such a change gives lookups of
  * the changed keys an unspecified row or RSK_CONN_NONE, never an access outside the table.  The other
  * columns need no rebuild.  The arrays are the caller's and do not move, so a call captured into a
  * hipGraph sees later row edits and rebuilds.
@@ -1079,6 +1082,144 @@ int rsk_conn_close_batch(rsk_ctx *ctx, const rsk_conn_table *tab, const rsk_conn
  * and copied to the other is valid there); sequential on the caller's thread; the IdBuf column at any alignment. */
 int rsk_conn_close_host(const rsk_conn_table *tab, const rsk_conn_rows *rows, const rsk_conn_close_in *in,
                         const rsk_conn_close_out *out, int nthreads);
+
+/* ---- conn create: fake-TCP conns made on the device table ------------------------------------------- */
+/* INetGroup::Input's miss path (conn/INetGroup.cpp:57-83): ConnOfIntKey fails, SNetGroup::CreateNetConn
+ * (server/SNetGroup.cpp:20-46) asks ServerNetManager::GetTcp (server/ServerNetManager.cpp:52-75) for the accepted
+ * socket and the TcpAckPool record of the packet's 4-tuple, builds a FakeTcp from them, Init()s it, and AddNetConn
+ * puts it into mConns and mConnMap; the packet that caused it, and every later packet of the key, is input to the
+ * new conn.  A client never creates from a packet (client/CNetGroup.cpp:11-13 returns nullptr): its conns come
+ * from DialTcpSync / DialTcpAsync followed by AddNetConn -- the list form.
+ *   receive  resolve -> rsk_conn_create_batch -> rsk_tcp_recv_ack_batch -> rsk_control_batch ->
+ *            rsk_conn_close_batch -> rsk_conn_pick_batch -> ...
+ * Offers.  The host's join of the accepted sockets (ServerNetManager::mPool) and the harvested handshakes
+ * (TcpAckPool): a caller-owned device list of m_max entries, the first min(*n_offer, m_max) in use (*n_offer is a
+ * device word).  An offer has src, dst, sp, dp in the orientation of the parse's TcpInfo of a DATA packet of the
+ * connection (the one FakeTcp is constructed with and the row stores), ack (the info.ack Wait2TransferInfo
+ * leaves) and flag; no seq (FakeTcp::Init never reads it).  It is matched by its 4-tuple alone
+ * (TcpCmpFn keys both pools by src, sp, dst, dp); of two offers with one tuple the lower index is the tuple's.
+ * COLUMN FORM (flags without RSK_CONN_CREATE_LIST), behind rsk_conn_resolve_batch whose conn / hit / miss / n_miss
+ * it continues; miss must be the resolve's (or an earlier call's) for the table as it is:
+ *   1. The considered packets are the first u_max packets with miss[i] == RSK_RECV_VALID, in packet order; no
+ *      other packet's key or tuple is read before step 8.
+ *   2. K_0 .. K_{k-1} = their distinct keys (conn_key, or (id, conn_key) with BY_ID) in first-arrival order,
+ *      f_j = the first considered packet of K_j.
+ *   3. K_j is offered iff the tuple of packet f_j (src, dst, sp, dp columns) has an offer that no key with a lower
+ *      f took and that was not consumed before (below).  Every other key is refused: it creates nothing, its
+ *      packets stay in miss, it is counted in *n_refused (CreateNetConn returning nullptr; the reference hands
+ *      such packets to mDefaultFakeConn).  DEVIATION: the reference retries CreateNetConn at every later packet
+ *      of the key; this call looks at f_j only.  A key's packets share their ports, so the tuples agree unless a
+ *      packet is forged.
+ *   4. The offered keys, in first-arrival order, take the vacant rows (RSK_CONN_LIVE clear) v_0 < v_1 < ...:
+ *      n_new = min(offered, vacant), n_full = the rest, whose offers are not consumed.
+ *   5. A new row: state = LIVE | ALIVE | RSK_CONN_NEW (INetConn's mAlive, mNew); conn_key and id from packet f_j
+ *      (the EncHead's key, never one made from the tuple: server/SNetGroup.cpp:29 records that bug); src, dst, sp,
+ *      dp, flag from the offer; seq = offer.ack + 1 and ack = offer.ack + 2 modulo 2^32 (tests/golden/tcpstate.npz);
+ *      with in->established_ms / in->ka_tries given, established_ms = now_ms and ka_tries = RSK_KA_NONE.  Every
+ *      column of every other row stays bytewise untouched.
+ *   6. Conn index: the new rows are inserted in place by rsk_conn_index_build's rule (compare-and-swap on a free
+ *      entry, the lowest row of a key wins) in a later launch than the one that writes the rows; no rebuild.
+ *      Bytes may differ from a rebuilt index, no lookup's result does.  A call that creates nothing writes no
+ *      byte of tab->index.
+ *   7. Pick index (out->pick, optional; precondition as rsk_conn_close_batch: current for the state found).
+ *      Afterwards every rsk_conn_pick_batch result equals the result on an index freshly built over the new
+ *      state, and so do the header words and pick_counts (written by every call that has `pick`).  A new row is
+ *      a candidate of its group at its place in ascending row order.  A group without candidates (no entry, or
+ *      one the close emptied) takes the first entry of its IdBuf's probe chain that is free or emptied, whichever
+ *      IdBuf the emptied one held: entries are reused, so a table may see any number of IdBufs in its life and a
+ *      group always finds an entry.  Probe chains only shorten again with rsk_conn_pick_build: once every entry
+ *      has been used, a lookup of an IdBuf without candidates walks all of `group`; a server with heavy IdBuf
+ *      churn rebuilds now and then.  The bytes may differ from a fresh
+ *      build's (groups that had no candidate stand behind the others in cand).  When nothing was created no byte
+ *      of it is written.  Every value read from it is bounded before use.
+ *   8. Every packet of the batch with miss[i] == VALID whose key now resolves gets conn[i] = row, hit[i] = 1
+ *      (when given) and miss[i] = RSK_RECV_DROP; *n_miss = the packets still missing; every other packet's
+ *      columns stay untouched.  rsk_tcp_recv_ack_batch(conn, hit, ...) then advances the new rows' ack as
+ *      FakeTcp::OnRecv does for the packet that created the conn.
+ *   9. new_rows[j], new_first[j], new_offer[j] = the j-th new conn's row, first packet and offer;
+ *      offer_row[o] = the row offer o became or RSK_CONN_NONE, over the first min(*n_offer, m_max) offers;
+ *      *n_new, *n_full, *n_refused are written, not accumulated; nothing behind the lists' ends is written.
+ *  10. Repeat calls.  With u_max below the missing packets the caller repeats while n_miss > 0 && n_full == 0 &&
+ *      n_new > 0.  The consumed offers are LEFT IN PLACE and the later calls carry RSK_CONN_CREATE_REPEAT: then an
+ *      offer whose offer_row entry is not RSK_CONN_NONE on entry was consumed, it still is its tuple's offer and
+ *      refuses every key, and its entry is kept.  The sequence gives the rows and the conn column of one call
+ *      with u_max >= n as long as each call's considered packets hold an offered key: packets of refused keys
+ *      stay missing and are considered again, so u_max should exceed what a batch can hold of those.
+ * LIST FORM (RSK_CONN_CREATE_LIST, n == 0, no packet columns): a client's dials and redials (AddNetConn after
+ * DialTcpSync, the redial behind rsk_conn_close_batch's closed_rows), or a host that does the matching itself.
+ * Every offer also has conn_key and, with BY_ID, id.  The first min(*n_offer, m_max) offers, in list order, that
+ * carry a key not LIVE in the table and not carried by a lower offer take the vacant rows by 4-7 with the key
+ * from the offer; the others are counted in *n_refused.  Outputs: offer_row, new_rows, new_offer, the counts.
+ * work: rsk_conn_create_bytes(u_max, m_max, capacity, table flags) bytes, 16-B aligned, caller-owned, contents do
+ * not matter, one per stream that runs the call.  With UI = max(u_max, m_max), M = min(m_max, capacity),
+ * S(x) = the power of two >= 2 x (at least 4) and every term rounded up to 4, it is 4 * (16 + 2 * ceil(UI / 64) +
+ * S(UI) + 2 UI + S(m_max) + 2 m_max + 10 M + S(M) + 2 * capacity) bytes: it depends on these values only.
+ * Launches: a linear chain of kernels on `stream`, no host state and no memset node; it captures into a hipGraph
+ * and replays on edited columns and offers.  Per-tile counts live in the control path's per-stream scratch
+ * (rsk_reserve_stream before a capture).  No block waits on another, nothing spins, every probe loop is bounded
+ * by its table's size, a row's state byte is written by the one lane that owns the row, no block reads a region
+ * of an index that another block of the same launch writes.  When nothing is missing, or no missing packet
+ * matches an offer, the later launches leave at once.  The order of the new candidates among the groups is a
+ * rank over the new conns of the call computed by all blocks; no pass walks the capacity or n
+ * on one block.  COST: on a RSK_CONN_BY_ID table with a pick index that rank takes n_new^2 key comparisons (spread
+ * over the device): it grows with the square of the conns born in ONE call, 4.5 ms at 210 K on an MI355X against
+ * 0.16 ms without BY_ID; a caller that bears more splits the call (u_max / m_max).
+ * RSK_EINVAL: a NULL ctx, tab, rows, in, out or work; a table a lookup cannot use or without state, src, dst, sp,
+ * dp, seq, ack or flag; a writable alias that is not the table's pointer; u_max 0 (column form) or above 2^24,
+ * m_max 0 or above 2^21; unknown flags; column form with n > 0 and a NULL miss, conn, conn_key or tuple column, or
+ * id missing with BY_ID; list form with n != 0, without the offers' conn_key, or without their id with BY_ID; a
+ * NULL offer column or n_offer; new_rows, new_first or new_offer without n_new; REPEAT without offer_row; work,
+ * index or pick not 16-B aligned, an id column not 8-B aligned; a capacity outside [1, RSK_CONN_MAX_ROWS];
+ * n > RSK_MAX_BATCH. */
+#define RSK_CONN_CREATE_LIST   0x1u  /* list form: the offers carry the keys, no packet columns            */
+#define RSK_CONN_CREATE_REPEAT 0x2u  /* offer_row is in/out: an entry that names a row marks a consumed offer */
+uint64_t rsk_conn_create_bytes(uint32_t u_max, uint32_t m_max, uint32_t capacity, uint32_t table_flags); /* 0: bad */
+
+typedef struct rsk_conn_create_rows {  /* writable aliases of the table's columns */
+    uint8_t *state; uint64_t *conn_key; uint8_t *id; uint32_t *src, *dst; uint16_t *sp, *dp;
+    uint32_t *seq, *ack; uint8_t *flag;
+} rsk_conn_create_rows;
+
+typedef struct rsk_conn_offers {
+    const uint32_t *src, *dst;   /* [m_max] */
+    const uint16_t *sp, *dp;     /* [m_max] */
+    const uint32_t *ack;         /* [m_max] info.ack behind Wait2TransferInfo */
+    const uint8_t  *flag;        /* [m_max] */
+    const uint64_t *conn_key;    /* [m_max] list form only */
+    const uint8_t  *id;          /* [m_max*8], 8-B aligned; list form with BY_ID only */
+    const uint32_t *n_offer;     /* [1] device word */
+    uint32_t m_max;
+} rsk_conn_offers;
+
+typedef struct rsk_conn_create_in {
+    const uint8_t  *id;          /* [n*8] dec->id, 8-B aligned; BY_ID */
+    const uint64_t *conn_key;    /* [n] dec->conn_key */
+    const uint32_t *src, *dst;   /* [n] the parse's TcpInfo */
+    const uint16_t *sp, *dp;     /* [n] */
+    rsk_conn_offers offers;
+    uint32_t u_max;              /* considered packets per call */
+    uint32_t flags;              /* RSK_CONN_CREATE_* */
+    uint64_t now_ms;
+    uint64_t *established_ms;    /* [capacity] optional */
+    uint8_t  *ka_tries;          /* [capacity] optional */
+    void *work;
+} rsk_conn_create_in;
+
+typedef struct rsk_conn_create_out {
+    uint32_t *conn;  uint8_t *hit;  int8_t *miss;  uint32_t *n_miss;  /* the resolve's, continued (column form) */
+    uint32_t *new_rows, *new_first, *new_offer;   /* [min(m_max, capacity)] optional; new_first column form only */
+    uint32_t *offer_row;                          /* [m_max] optional */
+    uint32_t *n_new, *n_full, *n_refused;         /* [1] optional */
+    uint32_t *pick, *pick_counts;                 /* as rsk_conn_close_out */
+} rsk_conn_create_out;
+
+int rsk_conn_create_batch(rsk_ctx *ctx, const rsk_conn_table *tab, const rsk_conn_create_rows *rows, uint32_t n,
+                          const rsk_conn_create_in *in, const rsk_conn_create_out *out, void *stream);
+/* The twin: host pointers, the same rules and outputs, the same work size (it need not use it) and index
+ * layouts: a table created on one side and copied to the other is valid there; sequential on the caller's
+ * thread; the id columns bytewise at any alignment. */
+int rsk_conn_create_host(const rsk_conn_table *tab, const rsk_conn_create_rows *rows, uint32_t n,
+                         const rsk_conn_create_in *in, const rsk_conn_create_out *out, int nthreads);
 
 /* ---- conv table: a DATA packet's conv, the convs' activity counts and their flush ------------------ */
 /* The reference's last lookup before a payload reaches anybody: on a server SubGroup::OnRecv looks

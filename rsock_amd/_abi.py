@@ -55,6 +55,7 @@ KA_MAX_RETRY = 3
 CONV_BY_DST, CONV_BY_ID = 0x1, 0x2
 CONV_CLOSE_HOLD = 0x1
 CONN_CLOSE_REMOVE, CONN_CLOSE_SWEEP = 0x1, 0x2
+CONN_CREATE_LIST, CONN_CREATE_REPEAT = 0x1, 0x2
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -213,6 +214,28 @@ class ConnCloseIn(ctypes.Structure):
 class ConnCloseOut(ctypes.Structure):
     _fields_ = [("marked_rows", _vp), ("n_marked", _vp), ("closed_rows", _vp), ("n_closed", _vp), ("pick", _vp),
                 ("pick_counts", _vp)]
+
+
+class ConnCreateRows(ctypes.Structure):
+    _fields_ = [("state", _vp), ("conn_key", _vp), ("id", _vp), ("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp),
+                ("seq", _vp), ("ack", _vp), ("flag", _vp)]
+
+
+class ConnOffers(ctypes.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("ack", _vp), ("flag", _vp), ("conn_key", _vp),
+                ("id", _vp), ("n_offer", _vp), ("m_max", ctypes.c_uint32)]
+
+
+class ConnCreateIn(ctypes.Structure):
+    _fields_ = [("id", _vp), ("conn_key", _vp), ("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp),
+                ("offers", ConnOffers), ("u_max", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("now_ms", ctypes.c_uint64), ("established_ms", _vp), ("ka_tries", _vp), ("work", _vp)]
+
+
+class ConnCreateOut(ctypes.Structure):
+    _fields_ = [("conn", _vp), ("hit", _vp), ("miss", _vp), ("n_miss", _vp), ("new_rows", _vp), ("new_first", _vp),
+                ("new_offer", _vp), ("offer_row", _vp), ("n_new", _vp), ("n_full", _vp), ("n_refused", _vp),
+                ("pick", _vp), ("pick_counts", _vp)]
 
 
 class ConvTable(ctypes.Structure):
@@ -377,6 +400,13 @@ SIGNATURES = [
     ("rsk_conn_close_host", ctypes.c_int,
      [ctypes.POINTER(ConnTable), ctypes.POINTER(ConnRows), ctypes.POINTER(ConnCloseIn), ctypes.POINTER(ConnCloseOut),
       ctypes.c_int]),
+    ("rsk_conn_create_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_conn_create_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(ConnTable), ctypes.POINTER(ConnCreateRows), ctypes.c_uint32, ctypes.POINTER(ConnCreateIn),
+      ctypes.POINTER(ConnCreateOut), _vp]),
+    ("rsk_conn_create_host", ctypes.c_int,
+     [ctypes.POINTER(ConnTable), ctypes.POINTER(ConnCreateRows), ctypes.c_uint32, ctypes.POINTER(ConnCreateIn),
+      ctypes.POINTER(ConnCreateOut), ctypes.c_int]),
     ("rsk_conv_close_bytes", ctypes.c_uint64, [ctypes.c_uint32]),
     ("rsk_conv_close_batch", ctypes.c_int,
      [_vp, ctypes.POINTER(ConvTable), ctypes.POINTER(ConvRows), ctypes.c_uint32, ctypes.POINTER(ConvCloseIn),

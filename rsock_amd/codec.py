@@ -361,6 +361,18 @@ class ConnTable:
             raise RskError(f"rsk_conn_close_bytes: bad capacity {self.capacity}")
         return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
 
+    def abi_create_rows(self) -> _abi.ConnCreateRows:
+        """The writable aliases of the columns that conn_create_batch / conn_create_host take."""
+        return _abi.ConnCreateRows(*[_ptr(getattr(self, name)) for name, _, _ in _CONN_COLUMNS])
+
+    def create_work(self, u_max: int, m_max: int) -> torch.Tensor:
+        """The work buffer of conn_create_batch / conn_create_host for at most u_max considered packets and m_max
+        offers per call (rsk_conn_create_bytes), on the table's device; one per stream that runs the call."""
+        nbytes = lib().rsk_conn_create_bytes(u_max, m_max, self.capacity, self.flags)
+        if nbytes == 0:
+            raise RskError(f"rsk_conn_create_bytes: bad u_max {u_max} / m_max {m_max}")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
     def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
         """rsk_conn_index_build on `stream` (a device table, with its Codec), or the host twin (a "cpu"
         table, codec None).  n_dup [1] receives the LIVE rows that lost their key to a lower row."""
@@ -477,6 +489,69 @@ def conn_close_host(tab: ConnTable, work, close_rows=None, n_close=None, m_max: 
                                    ctypes.byref(cout), nthreads)
     if rc != 0:
         raise RskError(f"rsk_conn_close_host failed: rc={rc}")
+
+
+@dataclass
+class ConnOffers:
+    """The offers of conn_create_batch / conn_create_host (rsk_conn_offers): columns of m_max entries (torch
+    tensors on the table's device, or numpy arrays for the host twin) and the device word n_offer.  conn_key and
+    id are the list form's."""
+
+    src: object
+    dst: object
+    sp: object
+    dp: object
+    ack: object
+    flag: object
+    n_offer: object
+    conn_key: object = None
+    id: object = None
+    m_max: int | None = None
+
+    def abi(self) -> _abi.ConnOffers:
+        m = len(self.src) if self.m_max is None else int(self.m_max)
+        return _abi.ConnOffers(_addr(self.src), _addr(self.dst), _addr(self.sp), _addr(self.dp), _addr(self.ack),
+                               _addr(self.flag), _addr(self.conn_key), _addr(self.id), _addr(self.n_offer), m)
+
+
+def _conn_create_structs(tab, offers, work, kw):
+    """-> (n, rsk_conn_create_in, rsk_conn_create_out) from the keyword arguments of Codec.conn_create_batch."""
+    g = kw.get
+    flags = (_abi.CONN_CREATE_LIST if g("list_form") else 0) | (_abi.CONN_CREATE_REPEAT if g("repeat") else 0)
+    miss = g("miss")
+    n = g("n")
+    if n is None:
+        n = 0 if miss is None else len(miss)
+    cin = _abi.ConnCreateIn(_addr(g("id")), _addr(g("conn_key")), _addr(g("src")), _addr(g("dst")), _addr(g("sp")),
+                            _addr(g("dp")), offers.abi(), int(g("u_max") or 0), flags,
+                            int(g("now_ms") or 0) & 0xFFFFFFFFFFFFFFFF, _addr(g("established_ms")), _addr(g("ka_tries")),
+                            _addr(work))
+    cout = _abi.ConnCreateOut(_addr(g("conn")), _addr(g("hit")), _addr(miss), _addr(g("n_miss")), _addr(g("new_rows")),
+                              _addr(g("new_first")), _addr(g("new_offer")), _addr(g("offer_row")), _addr(g("n_new")),
+                              _addr(g("n_full")), _addr(g("n_refused")), _addr(tab.pick) if g("pick") else None,
+                              _addr(g("pick_counts")))
+    return int(n), cin, cout
+
+
+_CONN_CREATE_KW = frozenset(("n", "u_max", "id", "conn_key", "src", "dst", "sp", "dp", "conn", "hit", "miss", "n_miss",
+                             "list_form", "repeat", "now_ms", "established_ms", "ka_tries", "new_rows", "new_first",
+                             "new_offer", "offer_row", "n_new", "n_full", "n_refused", "pick", "pick_counts"))
+
+
+def conn_create_bytes(u_max: int, m_max: int, capacity: int, by_id: bool = False) -> int:
+    """rsk_conn_create_bytes: the work buffer's size, 0 for bad arguments."""
+    return int(lib().rsk_conn_create_bytes(u_max, m_max, capacity, _abi.CONN_BY_ID if by_id else 0))
+
+
+def conn_create_host(tab: ConnTable, offers: ConnOffers, work, nthreads: int = 1, **kw) -> None:
+    """rsk_conn_create_host on a "cpu" ConnTable (no GPU); the keyword arguments of Codec.conn_create_batch."""
+    if set(kw) - _CONN_CREATE_KW:
+        raise TypeError(f"conn_create_host: unknown arguments {sorted(set(kw) - _CONN_CREATE_KW)}")
+    n, cin, cout = _conn_create_structs(tab, offers, work, kw)
+    rc = lib().rsk_conn_create_host(ctypes.byref(tab.abi()), ctypes.byref(tab.abi_create_rows()), n, ctypes.byref(cin),
+                                    ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_conn_create_host failed: rc={rc}")
 
 
 _MSG_COLUMNS = (("msg_cmd", torch.uint8, 1), ("msg_body", torch.int64, 1), ("msg_id", torch.uint8, 8),
@@ -1189,6 +1264,26 @@ class Codec:
                                         n_marked, closed_rows, n_closed, pick, pick_counts)
         _check(lib().rsk_conn_close_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_rows()),
                                           ctypes.byref(cin), ctypes.byref(cout), _stream(stream)), "rsk_conn_close_batch")
+
+    def conn_create_batch(self, tab: "ConnTable", offers: "ConnOffers", work, stream=None, **kw) -> None:
+        """INetGroup::Input's miss path -> CreateNetConn -> AddNetConn on the device table (rsk_conn_create_batch).
+        Column form, behind conn_resolve_batch: conn, hit, miss, n_miss (the resolve's, continued), the packets'
+        conn_key, id (by_id), src, dst, sp, dp and u_max; the distinct keys of the first u_max missing packets
+        whose first packet's 4-tuple has an offer take the vacant rows in first-arrival order.  List form
+        (list_form=True): the offers carry conn_key (and id) themselves.  Outputs: new_rows / new_first /
+        new_offer [min(m_max, capacity)], offer_row [m_max], n_new, n_full, n_refused; repeat=True makes
+        offer_row in/out (a consumed offer refuses).  established_ms / ka_tries (with now_ms) are set for the new
+        rows when given.  pick=True keeps tab.pick current; pick_counts [2].  work = tab.create_work(u_max,
+        m_max), one per stream.  Captures into a graph after reserve(stream=...)."""
+        if set(kw) - _CONN_CREATE_KW:
+            raise TypeError(f"conn_create_batch: unknown arguments {sorted(set(kw) - _CONN_CREATE_KW)}")
+        n, cin, cout = _conn_create_structs(tab, offers, work, kw)
+        _check(lib().rsk_conn_create_batch(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(tab.abi_create_rows()), n,
+                                           ctypes.byref(cin), ctypes.byref(cout), _stream(stream)),
+               "rsk_conn_create_batch")
+
+    conn_create_host = staticmethod(conn_create_host)
+    conn_create_bytes = staticmethod(conn_create_bytes)
 
     def conv_close_batch(self, tab: "ConvTable", close_rows=None, n_close=None, m_max: int | None = None, work=None,
                          rst_first=None, ctl_kind=None, conv_row=None, unknown=None, n_unknown=None, hold: bool = False,

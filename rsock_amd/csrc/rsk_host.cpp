@@ -7,12 +7,14 @@
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/rsk_codec.h"
 #include "rsk_conn.h"
+#include "rsk_conn_create.h"
 #include "rsk_conv_create.h"
 #include "rsk_pick.h"
 
@@ -686,6 +688,210 @@ extern "C" int rsk_conn_close_host(const rsk_conn_table *t, const rsk_conn_rows 
     if (n_closed) index_build_host(HostConnTab{t}, t->index, t->state, cap, by_id, nullptr);
     if (out->n_marked) *out->n_marked = n_marked;
     if (out->n_closed) *out->n_closed = n_closed;
+    return RSK_OK;
+}
+
+// ---- conn create (rsk_conn_create_batch): the host twin; the argument rules and the row's seq / ack in
+// rsk_conn_create.h ----
+extern "C" uint64_t rsk_conn_create_bytes(uint32_t u_max, uint32_t m_max, uint32_t capacity, uint32_t flags) {
+    if ((flags & ~RSK_CONN_BY_ID) || capacity < 1u || capacity > RSK_CONN_MAX_ROWS) return 0;
+    if (u_max > rsk::kCreateMaxU || m_max == 0u || m_max > rsk::kCcMaxOffers) return 0;
+    return 4ull * rsk::conn_create_layout(u_max, m_max, capacity).words;
+}
+
+namespace {
+
+// The pick index over the state as it is, keeping the entry of every group that has candidates where it is: an
+// IdBuf without one takes the first entry of its probe chain that is free or that rsk_conn_close_host left without
+// candidates.  Every pick is what a fresh build gives; a walk over a garbage index is
+// bounded and leaves the id without a group.
+void pick_refresh_host(const rsk_conn_table *t, uint32_t *pick) {
+    constexpr uint8_t kUp = RSK_CONN_LIVE | RSK_CONN_ALIVE;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0;
+    const uint32_t cap = t->capacity, slots = rsk::conn_slots(cap), c4 = (cap + 3u) & ~3u;
+    const rsk::PickLayout l = rsk::pick_layout(cap, by_id);
+    std::memset(pick + l.cand, 0xFF, 4ull * 2u * c4);  // cand and pos
+    uint32_t total = 0, groups = 0;
+    if (!by_id) {
+        for (uint32_t r = 0; r < cap; ++r)
+            if ((t->state[r] & kUp) == kUp) {
+                pick[l.pos + r] = total;
+                pick[l.cand + total++] = r;
+            }
+        groups = total != 0u;
+    } else {
+        std::vector<uint32_t> cnt(slots, 0u), order, slot_of(cap, rsk::kConnEmpty);
+        std::vector<uint8_t> mine(slots, 0);  // the entry was given to an IdBuf by this pass
+        for (uint32_t r = 0; r < cap; ++r) {
+            if ((t->state[r] & kUp) != kUp) continue;
+            const uint64_t id = load64(t->id + 8ull * r);
+            // the IdBuf's entry: one this pass gave it, or the one its candidates have; else the first entry of its
+            // chain that is free or that a close left without candidates (whatever IdBuf that one holds: to every
+            // pick an emptied group is one without an entry), so the entries in use stay bounded by the groups
+            uint32_t s = rsk::conn_home(0ull, id, slots), found = rsk::kConnEmpty, take = rsk::kConnEmpty;
+            for (uint32_t step = 0; step < slots; ++step, s = rsk::conn_next(s, slots)) {
+                const uint32_t *g = pick + l.group + 4ull * s;
+                if (g[3] == 0u) {  // free: the chain ends
+                    if (take == rsk::kConnEmpty) take = s;
+                    break;
+                }
+                uint64_t gid;
+                std::memcpy(&gid, g, 8);
+                const bool has = g[2] < cap && g[3] <= cap - g[2];
+                if (gid == id && (mine[s] || has)) { found = s; break; }
+                if (take == rsk::kConnEmpty && !mine[s] && g[2] == rsk::kPickGoneOff && g[3] == rsk::kPickGoneCnt) take = s;
+            }
+            if (found == rsk::kConnEmpty && take != rsk::kConnEmpty) {
+                uint32_t *g = pick + l.group + 4ull * take;
+                std::memcpy(g, &id, 8);
+                g[2] = rsk::kPickTakenOff;
+                g[3] = rsk::kPickGoneCnt;
+                mine[take] = 1;
+                found = take;
+            }
+            if (found == rsk::kConnEmpty) continue;
+            if (cnt[found]++ == 0u) order.push_back(found);
+            slot_of[r] = found;
+        }
+        for (uint32_t s = 0; s < slots; ++s) {  // entries whose group has no candidate (any more)
+            uint32_t *g = pick + l.group + 4ull * s;
+            if (g[3] != 0u && cnt[s] == 0u) { g[2] = rsk::kPickGoneOff; g[3] = rsk::kPickGoneCnt; }
+        }
+        for (uint32_t s : order) {  // in the order of the groups' lowest candidate rows
+            uint32_t *g = pick + l.group + 4ull * s;
+            g[2] = total;
+            g[3] = 0u;
+            total += cnt[s];
+            ++groups;
+        }
+        for (uint32_t r = 0; r < cap; ++r) {
+            if (slot_of[r] == rsk::kConnEmpty) continue;
+            uint32_t *g = pick + l.group + 4ull * slot_of[r];
+            pick[l.pos + r] = g[3];
+            pick[l.cand + g[2] + g[3]++] = r;
+        }
+    }
+    pick[0] = total;
+    pick[1] = groups;
+}
+
+}  // namespace
+
+// The walk of the header's rules in item order: the first arrivals of the considered packets (or the offers of
+// the list form), each looking for its offer, take the vacant rows; then one pass over the batch for the
+// packets that now resolve.  `work` is not used.
+extern "C" int rsk_conn_create_host(const rsk_conn_table *t, const rsk_conn_create_rows *rows, uint32_t n,
+                                    const rsk_conn_create_in *in, const rsk_conn_create_out *out, int /*nthreads*/) {
+    if (!rsk::conn_create_args_ok(t, rows, n, in, out, false)) return RSK_EINVAL;
+    const bool by_id = (t->flags & RSK_CONN_BY_ID) != 0, list = (in->flags & RSK_CONN_CREATE_LIST) != 0;
+    const bool repeat = (in->flags & RSK_CONN_CREATE_REPEAT) != 0;
+    const rsk_conn_offers &of = in->offers;
+    const uint32_t cap = t->capacity, no = *of.n_offer < of.m_max ? *of.n_offer : of.m_max;
+    const uint32_t m = of.m_max < cap ? of.m_max : cap;
+    const HostConnTab h{t};
+    typedef std::pair<uint64_t, uint64_t> K2;
+    // items and their keys
+    std::vector<uint32_t> items;
+    if (list) {
+        for (uint32_t o = 0; o < no; ++o) items.push_back(o);
+    } else {
+        for (uint32_t i = 0; i < n && items.size() < in->u_max; ++i)
+            if (out->miss[i] == RSK_RECV_VALID) items.push_back(i);
+    }
+    auto item_key = [&](uint32_t x) {
+        return list ? K2(of.conn_key[x], by_id ? load64(of.id + 8ull * x) : 0ull)
+                    : K2(in->conn_key[x], by_id ? load64(in->id + 8ull * x) : 0ull);
+    };
+    std::map<std::pair<K2, uint64_t>, uint32_t> tuple_offer;  // column form: a tuple's lowest offer
+    std::vector<uint8_t> taken(no, 0);
+    if (!list)
+        for (uint32_t o = 0; o < no; ++o) {
+            tuple_offer.emplace(std::make_pair(K2(of.src[o], of.dst[o]), rsk::tuple_ports(of.sp[o], of.dp[o])), o);
+            if (repeat && out->offer_row[o] != RSK_CONN_NONE) taken[o] = 1;
+        }
+    std::map<K2, uint32_t> seen;
+    std::vector<uint32_t> got_item, got_offer;  // the offered keys, in first-arrival order
+    uint32_t keys = 0;
+    for (uint32_t x : items) {
+        const K2 k = item_key(x);
+        if (!seen.emplace(k, x).second) continue;
+        ++keys;
+        uint32_t o = RSK_CONN_NONE;
+        if (list) {
+            if (rsk::conn_lookup(h, cap, by_id, k.first, k.second) == rsk::kConnEmpty) o = x;
+        } else {
+            auto it = tuple_offer.find(std::make_pair(K2(in->src[x], in->dst[x]), rsk::tuple_ports(in->sp[x], in->dp[x])));
+            if (it != tuple_offer.end() && !taken[it->second]) {
+                o = it->second;
+                taken[o] = 1;
+            }
+        }
+        if (o == RSK_CONN_NONE) continue;
+        got_item.push_back(x);
+        got_offer.push_back(o);
+    }
+    if (list) keys = no;  // every offer is asked; the ones that repeat a key are refused too
+    if (out->offer_row)
+        for (uint32_t o = 0; o < no; ++o)
+            if (!(repeat && out->offer_row[o] != RSK_CONN_NONE)) out->offer_row[o] = RSK_CONN_NONE;
+    const uint32_t slots = rsk::conn_slots(cap);
+    uint32_t n_new = 0, v = 0;
+    for (size_t q = 0; q < got_item.size() && n_new < m; ++q) {
+        while (v < cap && (rows->state[v] & RSK_CONN_LIVE)) ++v;
+        if (v == cap) break;
+        const uint32_t x = got_item[q], o = got_offer[q];
+        const K2 k = item_key(x);
+        rows->conn_key[v] = k.first;
+        if (by_id) std::memcpy(rows->id + 8ull * v, &k.second, 8);
+        rows->src[v] = of.src[o];
+        rows->dst[v] = of.dst[o];
+        rows->sp[v] = of.sp[o];
+        rows->dp[v] = of.dp[o];
+        rows->flag[v] = of.flag[o];
+        rows->seq[v] = rsk::create_seq(of.ack[o]);
+        rows->ack[v] = rsk::create_ack(of.ack[o]);
+        if (in->established_ms) in->established_ms[v] = in->now_ms;
+        if (in->ka_tries) in->ka_tries[v] = (uint8_t)RSK_KA_NONE;
+        rows->state[v] = (uint8_t)(RSK_CONN_LIVE | RSK_CONN_ALIVE | RSK_CONN_NEW);
+        uint32_t s = rsk::conn_home(k.first, k.second, slots);  // rsk_conn_index_build's rule, bounded
+        for (uint32_t step = 0; step < slots; ++step, s = rsk::conn_next(s, slots)) {
+            const uint32_t e = t->index[s];
+            if (e == rsk::kConnEmpty) { t->index[s] = v; break; }
+            if (e >= cap) break;
+            if (h.key(e) == k.first && (!by_id || h.id(e) == k.second)) {
+                if (v < e) t->index[s] = v;
+                break;
+            }
+        }
+        if (out->new_rows) out->new_rows[n_new] = v;
+        if (out->new_first && !list) out->new_first[n_new] = x;
+        if (out->new_offer) out->new_offer[n_new] = o;
+        if (out->offer_row) out->offer_row[o] = v;
+        ++n_new;
+        ++v;
+    }
+    if (out->pick) {
+        if (n_new) pick_refresh_host(t, out->pick);
+        if (out->pick_counts) {
+            out->pick_counts[0] = out->pick[1];
+            out->pick_counts[1] = out->pick[0];
+        }
+    }
+    if (!list) {
+        uint32_t left = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (out->miss[i] != RSK_RECV_VALID) continue;
+            const uint32_t row = rsk::conn_lookup(h, cap, by_id, in->conn_key[i], by_id ? load64(in->id + 8ull * i) : 0ull);
+            if (row == RSK_CONN_NONE) { ++left; continue; }
+            out->conn[i] = row;
+            if (out->hit) out->hit[i] = 1;
+            out->miss[i] = RSK_RECV_DROP;
+        }
+        if (out->n_miss) *out->n_miss = left;
+    }
+    if (out->n_new) *out->n_new = n_new;
+    if (out->n_full) *out->n_full = (uint32_t)got_item.size() - n_new;
+    if (out->n_refused) *out->n_refused = keys - (uint32_t)got_item.size();
     return RSK_OK;
 }
 

@@ -117,6 +117,8 @@ RSK_CONN_HD uint32_t pick_row(const P &p, uint32_t capacity, uint32_t off, uint3
 //   goff     [C4]   BY_ID only: per new position, the old offset of the entry's group (kConnEmpty: none)
 constexpr uint32_t kPickTile = 1024u;                        // entries of cand per tile of the update
 constexpr uint32_t kPickGoneOff = 0xFFFFFFFFu, kPickGoneCnt = 1u;  // {off, cnt} of a group without candidates
+// off of an emptied or free entry that rsk_conn_create_batch is giving to a new group (between two of its launches)
+constexpr uint32_t kPickTakenOff = 0xFFFFFFFEu;
 
 struct CloseLayout {
     uint32_t k, cand, goff, words;  // word offsets into work, and the total

@@ -1,0 +1,774 @@
+"""TEST INFRASTRUCTURE: rsk_conn_create_batch (include/rsk_codec.h) restated in numpy, the checkers and the
+scenarios the CPU and GPU tests share (the device is a parameter: "cpu" drives the host twin, a cuda device the
+batch call of a Codec).
+
+  create_ref    the contract as the reference's sequential walk in packet order (INetGroup::Input's miss path,
+                conn/INetGroup.cpp:57-83 -> SNetGroup::CreateNetConn, server/SNetGroup.cpp:20-46): for each missing
+                packet look the key up; on a miss look the packet's 4-tuple up in the offers; create in the lowest
+                vacant row; route this and every later packet of the key to it.  Two rules make it a batch rule:
+                (1) FIRST PACKET ONLY -- a key is decided at its first considered packet, a key that found no offer
+                (or no row) there is not asked again at its later packets; (2) LOWEST f_j WINS -- of the keys whose
+                first packets name one offer the one that comes first in the batch takes it (what a walk in packet
+                order does anyway), and the offer stays taken even if the table was full.
+  Harness       conn_close_ref.Harness plus create(): a table on the device under test with its numpy image; every
+                call is followed by the checkers: every table column bytewise, every output list with sentinel
+                bytes behind its end, conn / hit / miss, every lookup against conn_ref on the new state (index as
+                left, then rebuilt), every pick against pick_ref.rule_ref and a freshly built pick index, and
+                nothing written where nothing changed.
+Every comparison is exact."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from rsock_amd import _abi as A
+from tests import conn_close_ref as K
+from tests import conn_ref as CR
+from tests import pick_ref as P
+
+NONE = A.CONN_NONE
+LIVE, ALIVE, NEW, UP = K.LIVE, K.ALIVE, K.NEW, K.UP
+BORN = LIVE | ALIVE | NEW
+VALID, DROP = A.RECV_VALID, A.RECV_DROP
+SENT, SENT32 = K.SENT, K.SENT32
+CAPACITIES = (1, 2, 257, 1023, 1024, 1025, 4097)
+GPU_CAPACITIES = (1, 2, 257, 1025, 4097)
+SIZES = (0, 1, 65, 2047, 2048, 2049, 6000)
+OFFER_COLS = (("src", np.uint32), ("dst", np.uint32), ("sp", np.uint16), ("dp", np.uint16), ("ack", np.uint32),
+              ("flag", np.uint8))
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------
+def create_ref(cols, by_id, offers, n_offer, m_max, batch=None, miss=None, conn=None, hit=None, u_max=0,
+               list_form=False, consumed=(), now_ms=0, est=None, ka=None):
+    """-> dict(cols, est, ka, conn, hit, miss, n_miss, new_rows, new_first, new_offer, offer_row, n_new, n_full,
+    n_refused).  offers: dict of columns (conn_key / id in list form); batch: dict(conn_key, id, src, dst, sp, dp).
+    consumed: the offers an earlier call of a repeat loop took (they still hold their tuple and refuse)."""
+    cols = {k: (None if v is None else v.copy()) for k, v in cols.items()}
+    cap = len(cols["state"])
+    no = min(int(n_offer), int(m_max))
+    est = None if est is None else est.copy()
+    ka = None if ka is None else ka.copy()
+    vacant = iter(np.nonzero((cols["state"] & LIVE) == 0)[0].tolist())
+    new_rows, new_first, new_offer = [], [], []
+    offer_row = np.full(no, NONE, np.uint32)
+    n_full = n_refused = 0
+
+    def make(row, key, idw, o, first):
+        cols["conn_key"][row] = key
+        if by_id:
+            cols["id"].reshape(-1, 8)[row] = np.array([idw], np.uint64).view(np.uint8)
+        for k in ("src", "dst", "sp", "dp", "flag"):
+            cols[k][row] = offers[k][o]
+        cols["seq"][row] = (int(offers["ack"][o]) + 1) & 0xFFFFFFFF
+        cols["ack"][row] = (int(offers["ack"][o]) + 2) & 0xFFFFFFFF
+        cols["state"][row] = BORN
+        if est is not None:
+            est[row] = now_ms
+        if ka is not None:
+            ka[row] = A.KA_NONE
+        new_rows.append(row)
+        new_first.append(first)
+        new_offer.append(o)
+        offer_row[o] = row
+
+    if list_form:
+        tmap, _ = CR.table_map(cols["state"], cols["conn_key"], cols["id"] if by_id else None)
+        ow = CR.id_words(offers["id"] if by_id else None, len(offers["conn_key"]))
+        seen = set()
+        for o in range(no):
+            k = (int(ow[o]), int(offers["conn_key"][o]))
+            if k in tmap or k in seen:
+                n_refused += 1
+                continue
+            seen.add(k)
+            row = next(vacant, None)
+            if row is None:
+                n_full += 1
+                continue
+            make(row, k[1], k[0], o, 0)
+        out = {}
+    else:
+        n = len(miss)
+        miss, conn = np.asarray(miss, np.int8).copy(), np.asarray(conn, np.uint32).copy()
+        hit = None if hit is None else np.asarray(hit, np.uint8).copy()
+        w = CR.id_words(batch["id"] if by_id else None, n)
+        tuple_offer = {}
+        for o in range(no):
+            tuple_offer.setdefault(tuple(int(offers[k][o]) for k in ("src", "sp", "dst", "dp")), o)
+        taken, decided = set(int(o) for o in consumed), set()
+        for i in np.nonzero(miss == VALID)[0][: int(u_max)].tolist():
+            k = (int(w[i]), int(batch["conn_key"][i]))
+            if k in decided:  # rule 1: the key's first packet decided
+                continue
+            decided.add(k)
+            o = tuple_offer.get(tuple(int(batch[c][i]) for c in ("src", "sp", "dst", "dp")))
+            if o is None or o in taken:
+                n_refused += 1
+                continue
+            taken.add(o)  # rule 2: it is this key's, whatever comes
+            row = next(vacant, None)
+            if row is None:
+                n_full += 1
+                continue
+            make(row, k[1], k[0], o, i)
+        tmap, _ = CR.table_map(cols["state"], cols["conn_key"], cols["id"] if by_id else None)
+        for i in np.nonzero(miss == VALID)[0].tolist():
+            row = tmap.get((int(w[i]), int(batch["conn_key"][i])))
+            if row is not None:
+                conn[i] = row
+                miss[i] = DROP
+                if hit is not None:
+                    hit[i] = 1
+        out = {"conn": conn, "hit": hit, "miss": miss, "n_miss": int((miss == VALID).sum())}
+    u32 = lambda a: np.array(a, np.uint32)  # noqa: E731
+    out.update(cols=cols, est=est, ka=ka, new_rows=u32(new_rows), new_first=u32(new_first), new_offer=u32(new_offer),
+               offer_row=offer_row, n_new=len(new_rows), n_full=n_full, n_refused=n_refused)
+    return out
+
+
+# ---- the harness -------------------------------------------------------------------------------------------
+class Harness(K.Harness):
+    """conn_close_ref.Harness with the keepalive columns and create()."""
+
+    def __init__(self, rc, cols, by_id, device, codec=None):
+        super().__init__(rc, cols, by_id, device, codec)
+        rng = np.random.default_rng(self.cap + 77)
+        self.est = rng.integers(0, 2**62, self.cap, dtype=np.uint64)
+        self.ka = rng.integers(0, 4, self.cap, dtype=np.uint64).astype(np.uint8)
+        self.t_est, self.t_ka = self.t(self.est, np.uint64), self.t(self.ka, np.uint8)
+        self.works = {}
+
+    def moved(self, device, codec=None):
+        h = super().moved(device, codec)
+        h.__class__ = Harness
+        h.est, h.ka, h.works = self.est.copy(), self.ka.copy(), {}
+        h.t_est, h.t_ka = h.t(h.est, np.uint64), h.t(h.ka, np.uint8)
+        return h
+
+    def create_work(self, u_max, m_max):
+        if (u_max, m_max) not in self.works:
+            w = self.tab.create_work(u_max, m_max)
+            w.view(torch.uint8).fill_(0xA7)  # contents do not matter
+            self.works[(u_max, m_max)] = w
+        return self.works[(u_max, m_max)]
+
+    def offers_on(self, offers, n_offer, m_max, list_form):
+        cols = {k: self.t(np.ascontiguousarray(offers[k], dt), dt) for k, dt in OFFER_COLS}
+        if list_form:
+            cols["conn_key"] = self.t(offers["conn_key"], np.uint64)
+            cols["id"] = self.t(offers["id"], np.uint8) if self.by_id else None
+        return self.rc.ConnOffers(n_offer=self.t(np.array([n_offer]), np.uint32), m_max=m_max, **cols)
+
+    def raw_create(self, offers, n_offer, m_max, batch=None, conn=None, hit=None, miss=None, u_max=0, list_form=False,
+                   repeat=False, offer_row=None, pick=True, now_ms=0, stream=None, work=None):
+        """One call; -> dict of the outputs as numpy (lists whole, slack behind them)."""
+        dev, m = self.device, min(m_max, self.cap)
+        o = {k: K.filled(m + 3, torch.int32, dev) for k in ("new_rows", "new_first", "new_offer")}
+        o.update({k: K.filled(1, torch.int32, dev) for k in ("n_new", "n_full", "n_refused", "n_miss")})
+        o["offer_row"] = K.filled(m_max + 3, torch.int32, dev)
+        if offer_row is not None:
+            o["offer_row"][: len(offer_row)] = self.t(offer_row, np.uint32)
+        o["pick_counts"] = K.filled(2, torch.int32, dev) if pick else None
+        kw = dict(o, pick=pick, list_form=list_form, repeat=repeat, now_ms=now_ms, established_ms=self.t_est,
+                  ka_tries=self.t_ka, u_max=u_max)
+        cols = {}
+        if not list_form:
+            n = len(miss)
+            pad = lambda a, dt: self.t(np.concatenate([np.ascontiguousarray(a, dt), np.zeros(1, dt)]), dt)  # noqa: E731
+            cols = {"conn": pad(conn, np.uint32), "hit": None if hit is None else pad(hit, np.uint8), "miss": pad(miss, np.int8)}
+            kw.update(cols, n=n, conn_key=pad(batch["conn_key"], np.uint64),
+                      id=self.t(np.concatenate([batch["id"], np.zeros(8, np.uint8)]), np.uint8) if self.by_id else None,
+                      **{k: pad(batch[k], dt) for k, dt in OFFER_COLS[:4]})
+        else:
+            del kw["n_miss"], kw["new_first"]
+        w = self.create_work(u_max, m_max) if work is None else work
+        of = self.offers_on(offers, n_offer, m_max, list_form)
+        if self.codec is None:
+            self.rc.conn_create_host(self.tab, of, w, **kw)
+        else:
+            self.codec.conn_create_batch(self.tab, of, w, stream=stream, **kw)
+            torch.cuda.synchronize()
+        got = {k: K.host(v, np.uint32) for k, v in o.items() if v is not None}
+        if not list_form:
+            got["conn"] = K.host(cols["conn"], np.uint32)[:n]
+            got["miss"] = K.host(cols["miss"], np.int8)[:n]
+            got["hit"] = None if hit is None else K.host(cols["hit"], np.uint8)[:n]
+        return got
+
+    def compare(self, got, ref, m_max, n_offer, list_form):
+        k = ref["n_new"]
+        for c in ("n_new", "n_full", "n_refused"):
+            assert got[c][0] == ref[c], (c, got[c][0], ref[c])
+        for lst in ("new_rows", "new_offer") + (() if list_form else ("new_first",)):
+            assert np.array_equal(got[lst][:k], ref[lst]), (lst, got[lst][:8], ref[lst][:8])
+            assert bool((got[lst][k:] == SENT32).all()), lst + ": written behind its count"
+        if list_form:
+            assert bool((got["new_first"] == SENT32).all()) and got["n_miss"][0] == SENT32
+        no = min(n_offer, m_max)
+        assert np.array_equal(got["offer_row"][:no], ref["offer_row"]), "offer_row"
+        assert bool((got["offer_row"][no:] == SENT32).all()), "offer_row: written behind the offers"
+        if not list_form:
+            assert got["n_miss"][0] == ref["n_miss"], ("n_miss", got["n_miss"][0], ref["n_miss"])
+            for c in ("conn", "miss", "hit"):
+                assert (got[c] is None and ref[c] is None) or np.array_equal(got[c], ref[c]), c
+
+    def create(self, offers, n_offer=None, m_max=None, batch=None, status=None, u_max=None, list_form=False,
+               repeat=False, offer_row=None, pick=True, picks=True, now_ms=0x1234_5678_9ABC, hit=True, inputs=None):
+        """A call with every checker behind it; -> (the restatement's dict, the outputs).  Column form: the
+        resolve's conn / hit / miss come from conn_ref on the table's image (or `inputs`, an earlier call's)."""
+        m_max = len(offers["src"]) if m_max is None else m_max
+        n_offer = len(offers["src"]) if n_offer is None else n_offer
+        conn = miss = hitc = None
+        if not list_form:
+            n = len(batch["conn_key"])
+            u_max = max(n, 1) if u_max is None else u_max
+            if inputs is None:
+                tmap, _ = CR.table_map(self.cols["state"], self.cols["conn_key"], self.cols["id"] if self.by_id else None)
+                st = np.full(n, VALID, np.int8) if status is None else status
+                conn, hitc, miss, _ = CR.resolve_ref(tmap, st, batch["conn_key"], id=batch["id"] if self.by_id else None)
+            else:
+                conn, hitc, miss = inputs["conn"], inputs["hit"], inputs["miss"]
+            if not hit:
+                hitc = None
+        consumed = () if not repeat else np.nonzero(np.asarray(offer_row) != NONE)[0].tolist()
+        ref = create_ref(self.cols, self.by_id, offers, n_offer, m_max, batch, miss, conn, hitc, u_max or 0, list_form,
+                         consumed, now_ms, self.est, self.ka)
+        if repeat:  # a consumed offer keeps its entry
+            keep = np.asarray(offer_row, np.uint32)[: len(ref["offer_row"])]
+            ref["offer_row"] = np.where(ref["offer_row"] == NONE, keep, ref["offer_row"])
+        index0, pick0 = self.tab.index.clone(), self.tab.pick.clone()
+        got = self.raw_create(offers, n_offer, m_max, batch, conn, hitc, miss, u_max or 0, list_form, repeat, offer_row,
+                              pick, now_ms)
+        self.compare(got, ref, m_max, n_offer, list_form)
+        self.cols, self.est, self.ka = ref["cols"], ref["est"], ref["ka"]
+        self.compare_columns()
+        assert np.array_equal(K.host(self.t_est, np.uint64), self.est), "established_ms"
+        assert np.array_equal(K.host(self.t_ka, np.uint8), self.ka), "ka_tries"
+        self.removed -= set(ref["new_rows"].tolist())
+        self.killed -= set(ref["new_rows"].tolist())
+        if ref["n_new"] == 0:
+            assert bool((self.tab.index == index0).all()), "the conn index was written though nothing was created"
+            assert bool((self.tab.pick == pick0).all()), "the pick index was written though nothing was created"
+        if pick:
+            groups = P.candidates(self.cols["state"], self.cols["id"], self.by_id)
+            total = sum(len(g) for g in groups.values())
+            n_groups = sum(1 for g in groups.values() if len(g))
+            assert got["pick_counts"].tolist() == [n_groups, total], (got["pick_counts"], n_groups, total)
+            assert K.host(self.tab.pick[:4], np.uint32).tolist() == [total, n_groups, 0, 0]
+        else:
+            assert bool((self.tab.pick == pick0).all()), "the pick index was written though it was not given"
+        self.check_lookups()
+        if pick and picks:
+            self.check_picks()
+        return ref, got
+
+
+# ---- tables, batches and offers ------------------------------------------------------------------------------
+def table(capacity, by_id, seed=0, empty=False):
+    cols = K.grouped_table(capacity, by_id, seed)
+    if empty:
+        cols["state"][:] = np.random.default_rng(seed).choice(np.array([0, ALIVE, NEW], np.uint8), capacity)
+    return cols
+
+
+def new_conns(rng, cols, by_id, k, new_ids=0.3):
+    """k conns the table does not know: distinct keys and tuples, ids from the table's groups or new ones.
+    -> dict(conn_key [k], idw [k], src, dst, sp, dp, ack, flag)."""
+    cap = len(cols["state"])
+    key = (rng.permutation(max(k, 1))[:k].astype(np.uint64) + np.uint64(1)) * np.uint64(0x10001) + np.uint64(2**62)
+    w = CR.id_words(cols["id"] if by_id else None, cap)
+    idw = np.zeros(k, np.uint64)
+    if by_id:
+        fresh = rng.integers(2**40, 2**41, max(k // 3, 1), dtype=np.uint64)
+        idw = np.where(rng.random(k) < new_ids, fresh[rng.integers(0, len(fresh), k)], w[rng.integers(0, cap, k)])
+    t = rng.permutation(max(k, 1))[:k].astype(np.uint64)
+    return {"conn_key": key, "idw": idw, "src": (t + np.uint64(0x0A000000)).astype(np.uint32),
+            "dst": np.full(k, 0xC0A80001, np.uint32), "sp": (t % np.uint64(60000) + np.uint64(1024)).astype(np.uint16),
+            "dp": (t // np.uint64(60000) + np.uint64(443)).astype(np.uint16),
+            "ack": np.where(rng.random(k) < 0.1, 0xFFFFFFFF - rng.integers(0, 2, k), rng.integers(0, 2**32, k)).astype(np.uint32),
+            "flag": rng.integers(0, 256, k).astype(np.uint8)}
+
+
+def offers_of(nc, which=None, extra=None, list_form=False):
+    """The offers of the conns `which` (indices into nc, default all), in that order."""
+    which = np.arange(len(nc["conn_key"])) if which is None else np.asarray(which, np.int64)
+    o = {k: nc[k][which].copy() for k, _ in OFFER_COLS}
+    if list_form:
+        o["conn_key"] = nc["conn_key"][which].copy()
+        o["id"] = P.id_bytes(nc["idw"][which])
+    if len(which) == 0:  # a column of one unused entry: the call takes no NULL column
+        o = {k: np.zeros(1, v.dtype) for k, v in o.items()}
+        if list_form:
+            o["id"] = np.zeros(8, np.uint8)
+    return o
+
+
+def batch_of(rng, cols, by_id, nc, n, known=0.5, order=None):
+    """n packets: a share of them of LIVE conns of the table, the rest of the new conns nc (every new conn at least
+    once when n allows, in random order).  -> dict(conn_key, id, src, dst, sp, dp, which [n]: the new conn or -1)."""
+    cap, k = len(cols["state"]), len(nc["conn_key"])
+    live = np.nonzero(cols["state"] & LIVE)[0]
+    which = np.full(n, -1, np.int64)
+    if k:
+        new_at = rng.random(n) >= (known if len(live) else 0.0)
+        cnt = int(new_at.sum())
+        pick = np.concatenate([rng.permutation(k), rng.integers(0, k, max(cnt - k, 0))])[:cnt]
+        which[new_at] = rng.permutation(pick) if order is None else pick
+    rows = live[rng.integers(0, len(live), n)] if len(live) else np.zeros(n, np.int64)
+    w = CR.id_words(cols["id"] if by_id else None, cap)
+    isnew = which >= 0
+    wn = np.where(isnew, which, 0)
+    b = {"conn_key": np.where(isnew, nc["conn_key"][wn] if k else 0, cols["conn_key"][rows]).astype(np.uint64),
+         "id": P.id_bytes(np.where(isnew, nc["idw"][wn] if k else 0, w[rows]).astype(np.uint64)) if by_id else None,
+         "which": which}
+    for c, dt in OFFER_COLS[:4]:
+        b[c] = np.where(isnew, nc[c][wn] if k else 0, cols[c][rows]).astype(dt)
+    return b
+
+
+# ---- scenarios -------------------------------------------------------------------------------------------------
+def scenario_sizes(rc, capacity, n, by_id, device, codec=None):
+    """A random batch of n packets on a table of `capacity` rows: known conns, new conns with and without offers,
+    unclaimed offers; then what is left over again with more offers than the table has rows."""
+    rng = np.random.default_rng(capacity * 31 + n * 7 + by_id)
+    cols = table(capacity, by_id, seed=n % 5)
+    h = Harness(rc, cols, by_id, device, codec)
+    k = min(n, max(1, capacity // 2 + 2))
+    nc = new_conns(rng, cols, by_id, k)
+    b = batch_of(rng, cols, by_id, nc, n)
+    extra = new_conns(np.random.default_rng(5), cols, by_id, 3)
+    for c in extra:  # offers nobody claims
+        extra[c] = extra[c] + (np.uint64(7) if c == "conn_key" else 0)
+    extra["src"] = extra["src"] + np.uint32(0x01000000)
+    with_offer = rng.permutation(k)[: max(1, (2 * k) // 3)]
+    of = offers_of(nc, with_offer)
+    of = {c: np.concatenate([of[c], extra[c]]) for c, _ in OFFER_COLS}
+    ref, _ = h.create(of, batch=b)
+    made = ref["n_new"]
+    ref2, _ = h.create(offers_of(nc), batch=b, hit=False)  # every conn offered now: the table fills
+    return made + ref2["n_new"]
+
+
+def scenario_patterns(rc, capacity, by_id, device, codec=None, n=600):
+    """The issue's patterns on one table size."""
+    rng = np.random.default_rng(capacity * 13 + by_id)
+    cols = table(capacity, by_id, seed=3)
+    vac = int(((cols["state"] & LIVE) == 0).sum())
+    made = 0
+    # nothing missing; missing but no offers (n_offer == 0, and offers of other tuples)
+    h = Harness(rc, cols, by_id, device, codec)
+    nc0 = new_conns(rng, cols, by_id, 4)
+    if (cols["state"] & LIVE).any():
+        b = batch_of(rng, cols, by_id, new_conns(rng, cols, by_id, 0), n, known=1.0)
+        r, _ = h.create(offers_of(nc0), batch=b)
+        assert r["n_new"] == 0 and r["n_miss"] == 0
+    nc = new_conns(rng, cols, by_id, 5)
+    b = batch_of(rng, cols, by_id, nc, n)
+    r, _ = h.create(offers_of(nc), n_offer=0, batch=b)
+    assert r["n_new"] == 0 and r["n_refused"] == 5 and r["n_miss"] > 0
+    other = offers_of(nc)
+    other["sp"] = other["sp"] + np.uint16(1)
+    r, _ = h.create(other, batch=b)
+    assert r["n_new"] == 0 and r["n_refused"] == 5
+    # one new conn; all packets one new key
+    one = new_conns(rng, cols, by_id, 1)
+    r, _ = h.create(offers_of(one), batch=batch_of(rng, cols, by_id, one, n))
+    assert r["n_new"] == min(1, vac)
+    made += r["n_new"]
+    one = new_conns(np.random.default_rng(99), cols, by_id, 1)
+    one["conn_key"] += np.uint64(12345)
+    one["src"] += np.uint32(0x02000000)
+    r, _ = h.create(offers_of(one), batch=batch_of(rng, h.cols, by_id, one, n, known=0.0))
+    made += r["n_new"]
+    # every packet a different new key (more keys than rows: the table fills, n_full > 0, offers not consumed)
+    h = Harness(rc, cols, by_id, device, codec)
+    nc = new_conns(rng, cols, by_id, n)
+    r, _ = h.create(offers_of(nc), batch=batch_of(rng, cols, by_id, nc, n, known=0.0, order="arrival"))
+    assert r["n_new"] == min(n, vac) and r["n_full"] == n - r["n_new"]
+    made += r["n_new"]
+    # exactly full
+    if 0 < vac <= n:
+        h = Harness(rc, cols, by_id, device, codec)
+        nc = new_conns(rng, cols, by_id, vac)
+        r, _ = h.create(offers_of(nc), batch=batch_of(rng, cols, by_id, nc, max(n, vac), known=0.2))
+        assert r["n_new"] == vac and r["n_full"] == 0 and not ((h.cols["state"] & LIVE) == 0).any()
+        r, _ = h.create(offers_of(one), batch=batch_of(rng, h.cols, by_id, one, 50, known=0.0))
+        assert r["n_new"] == 0 and r["n_full"] == 1
+    # two keys claiming one offer (the earlier first packet wins); two offers with one tuple (the lower index is
+    # the tuple's); *n_offer > m_max
+    h = Harness(rc, cols, by_id, device, codec)
+    nc = new_conns(rng, cols, by_id, 6)
+    for c, _ in OFFER_COLS[:4]:
+        nc[c][1] = nc[c][0]  # conn 1 is forged onto conn 0's tuple
+    b = batch_of(rng, cols, by_id, nc, max(n, 12), known=0.3)
+    of = offers_of(nc, [0, 2, 3, 2, 4, 5])  # offer 3 repeats offer 1's tuple with another ack
+    of["ack"][3] ^= np.uint32(0x55)
+    r, _ = h.create(of, n_offer=9, m_max=5, batch=b)  # the offer of conn 5 lies behind m_max
+    first = {int(w): int(np.nonzero(b["which"] == w)[0][0]) for w in range(6)}
+    assert r["n_refused"] == 2 and r["n_new"] == min(4, vac)
+    if vac >= 4:
+        assert r["offer_row"][3] == NONE and r["offer_row"][1] != NONE
+        assert (first[0] < first[1]) == (int(r["new_first"][list(r["new_offer"]).index(0)]) == first[0])
+    made += r["n_new"]
+    return made
+
+
+def scenario_groups(rc, by_id, device, codec=None):
+    """New rows below, between and above a group's old candidates; a new group; group sizes crossing 63 / 64 / 65
+    and 1024 / 1025; a group reborn after a close emptied it (its entry is reused, the chains of other ids stay)."""
+    cap = 2300
+    rng = np.random.default_rng(cap + by_id)
+    cols = CR.random_columns(rng, cap, by_id=by_id)
+    gid = lambda g: np.uint64((0x9E3779B97F4A7C15 * (g + 1)) & (2**64 - 1))  # noqa: E731
+    w = np.zeros(cap, np.uint64)
+    # group A: rows 100..163 but 120 (63 candidates); group B: rows 300..1324 but 700 (1024 candidates); group C: rows
+    # 1500..1509.  Every other row is vacant (random_columns leaves state 0), so the vacant rows in order are 0..99
+    # (below A), 120 (between A's candidates), 164..299 (above A, below B), 700 (between B's), 1325.. (above B).
+    sizes = {0: 63, 1: 1024, 2: 10}
+    for g, (lo, hi) in enumerate(((100, 164), (300, 1325), (1500, 1510))):
+        cols["state"][lo:hi] = UP
+        w[lo:hi] = gid(g)
+    cols["state"][[120, 700]] = 0
+    if by_id:
+        cols["id"][:] = P.id_bytes(w)
+    h = Harness(rc, cols, by_id, device, codec)
+
+    def conns(k, g, salt):
+        nc = new_conns(np.random.default_rng(salt), cols, by_id, k)
+        nc["conn_key"] += np.uint64(salt * 1000003)
+        nc["src"] += np.uint32(salt << 20)
+        nc["idw"][:] = gid(g) if by_id else 0
+        return nc
+
+    # steps of one conn across the edges: A 63 -> 64 -> 65 (rows 0, 1: below), B 1024 -> 1025 (row 2: below); a new
+    # group D (rows 3, 4); then 100 conns of A take rows 5..99, 120 and 164..167 (below, between, above), 140 of B take
+    # 168..299, 700 and 1325..1331 (below, between, above), and a new group E of one
+    total = 0
+    for step, (k, g) in enumerate(((1, 0), (1, 0), (1, 1), (2, 3), (100, 0), (140, 1), (1, 4))):
+        nc = conns(k, g, step + 1)
+        r, _ = h.create(offers_of(nc), batch=batch_of(rng, h.cols, by_id, nc, 3 * k + 5, known=0.4))
+        assert r["n_new"] == k
+        total += k
+        sizes[g] = sizes.get(g, 0) + k
+        if by_id:  # the sizes the checkers have just seen
+            groups = P.candidates(h.cols["state"], h.cols["id"], True)
+            assert {int(gid(q)): m for q, m in sizes.items()} == {int(q): len(v) for q, v in groups.items()}
+        if step == 4:
+            assert set(r["new_rows"].tolist()) == set(range(5, 100)) | {120} | set(range(164, 168))
+        if step == 5:
+            assert set(r["new_rows"].tolist()) == set(range(168, 300)) | {700} | set(range(1325, 1332))
+    assert sizes[0] == 165 and sizes[1] == 1165
+    # the close empties group C (and D); then conns of C are born again
+    gone = np.concatenate([np.arange(1500, 1510), np.nonzero(CR.id_words(h.cols["id"] if by_id else None, cap) == gid(3))[0]])
+    h.close(close_rows=gone.astype(np.uint32), remove=True)
+    nc = conns(3, 2, 50)
+    r, _ = h.create(offers_of(nc), batch=batch_of(rng, h.cols, by_id, nc, 20, known=0.5))
+    assert r["n_new"] == 3
+    nc = conns(2, 3, 51)
+    r, _ = h.create(offers_of(nc, list_form=True), list_form=True)
+    assert r["n_new"] == 2
+    return total + 5
+
+
+def scenario_churn(rc, capacity, device, codec=None):
+    """More distinct IdBufs over a table's life than its pick index has group entries (the power of two >= 2 *
+    capacity, at least 4): every round fills the table with conns of fresh IdBufs in list form, checks every lookup and
+    pick, and removes them all.  The entries of emptied groups are given to new ones, so every conn stays reachable."""
+    slots = 4
+    while slots < 2 * capacity:
+        slots <<= 1
+    rng = np.random.default_rng(capacity)
+    cols = CR.random_columns(rng, capacity, by_id=True)
+    h = Harness(rc, cols, True, device, codec)
+    rounds = slots // capacity + 3
+    for rnd in range(rounds):
+        nc = new_conns(rng, h.cols, True, capacity)
+        nc["conn_key"] += np.uint64(rnd * 15485863)
+        nc["idw"] = (np.arange(capacity, dtype=np.uint64) + np.uint64(1 + rnd * capacity)) * np.uint64(0x9E3779B97F4A7C15)
+        r, _ = h.create(offers_of(nc, list_form=True), list_form=True)
+        assert r["n_new"] == capacity
+        if rnd % 2:  # a round in which some groups stay and grow while the others go
+            keep = np.arange(0, capacity, 3)
+            h.close(close_rows=np.setdiff1d(np.arange(capacity), keep).astype(np.uint32), remove=True)
+            again = {k: v[: len(keep) // 2 + 1].copy() for k, v in nc.items()}
+            again["conn_key"] = again["conn_key"] + np.uint64(1)
+            again["idw"] = nc["idw"][keep][: len(again["conn_key"])]
+            r, _ = h.create(offers_of(again, list_form=True), list_form=True)
+            assert r["n_new"] == min(len(again["conn_key"]), capacity - len(keep))
+        h.close(close_rows=np.arange(capacity, dtype=np.uint32), remove=True)
+    return rounds * capacity
+
+
+def scenario_repeat(rc, capacity, by_id, device, codec=None, n=900, u_max=32):
+    """u_max below the missing packets: the documented loop (consumed offers left in place, REPEAT) reaches the rows
+    and the conn column of one call with u_max >= n."""
+    rng = np.random.default_rng(capacity + 5 * by_id)
+    cols = table(capacity, by_id, seed=4)
+    vac = int(((cols["state"] & LIVE) == 0).sum())
+    nc = new_conns(rng, cols, by_id, min(n // 3, max(3, (2 * vac) // 3)))
+    for c, _ in OFFER_COLS[:4]:
+        nc[c][1] = nc[c][0]  # one refused key
+    b = batch_of(rng, cols, by_id, nc, n, known=0.3)
+    of = offers_of(nc)
+    one = Harness(rc, cols, by_id, device, codec)
+    want, _ = one.create(of, batch=b)
+    h = Harness(rc, cols, by_id, device, codec)
+    inputs, offer_row, calls, rows = None, np.full(len(of["src"]), NONE, np.uint32), 0, []
+    while True:
+        r, got = h.create(of, batch=b, u_max=u_max, repeat=calls > 0, offer_row=offer_row if calls else None,
+                          inputs=inputs, picks=False)
+        calls += 1
+        rows += r["new_rows"].tolist()
+        inputs, offer_row = {k: got[k] for k in ("conn", "hit", "miss")}, got["offer_row"][: len(of["src"])].copy()
+        if not (r["n_miss"] > 0 and r["n_full"] == 0 and r["n_new"] > 0):
+            break
+        assert calls < 200
+    assert calls > 2
+    for k, v in want["cols"].items():
+        assert v is None or np.array_equal(v, h.cols[k]), k
+    assert np.array_equal(inputs["conn"], want["conn"]) and np.array_equal(inputs["miss"], want["miss"])
+    assert rows == want["new_rows"].tolist() and np.array_equal(offer_row, want["offer_row"])
+    h.check_picks()
+    return calls
+
+
+def scenario_list(rc, capacity, by_id, device, codec=None):
+    """The list form: an empty table filled to capacity, a key already LIVE, a key repeated in the list, and the
+    redial after a close."""
+    rng = np.random.default_rng(capacity * 3 + by_id)
+    cols = table(capacity, by_id, empty=True)
+    h = Harness(rc, cols, by_id, device, codec)
+    nc = new_conns(rng, cols, by_id, capacity + 2)
+    of = offers_of(nc, list_form=True)
+    r, _ = h.create(of, list_form=True)
+    assert r["n_new"] == capacity and r["n_full"] == 2
+    r, _ = h.create(of, list_form=True)  # every key LIVE (or no row): nothing
+    assert r["n_new"] == 0 and r["n_refused"] == capacity and r["n_full"] == 2
+    closed = h.close(close_rows=rng.integers(0, capacity, capacity // 2 + 1).astype(np.uint32), remove=True)["closed_rows"]
+    k = len(closed)
+    w = CR.id_words(h.cols["id"] if by_id else None, capacity)
+    redial = {c: np.concatenate([h.cols[c][closed], h.cols[c][closed][:1]]) for c, _ in OFFER_COLS[:4]}
+    redial.update(ack=rng.integers(0, 2**32, k + 1).astype(np.uint32), flag=np.full(k + 1, 0x18, np.uint8),
+                  conn_key=np.concatenate([h.cols["conn_key"][closed], h.cols["conn_key"][closed][:1]]),
+                  id=P.id_bytes(np.concatenate([w[closed], w[closed][:1]])))
+    dup = len(set(zip(w[closed].tolist(), h.cols["conn_key"][closed].tolist())))
+    r, _ = h.create(redial, list_form=True)  # the last offer repeats the first one's key
+    assert r["n_new"] == dup and r["n_refused"] == k + 1 - dup
+    return capacity + k
+
+
+def scenario_tcpstate(rc, name, device, codec=None):
+    """Rows created from the conns of tests/golden/tcpstate.npz hold the recorded mInfo.seq / mInfo.ack after
+    FakeTcp::Init."""
+    from tests import tcpstate_golden as T
+
+    s = T.script(name)
+    info = np.asarray(s["info"])
+    k = len(info)
+    cols = CR.random_columns(np.random.default_rng(k), k + 3, by_id=False)
+    h = Harness(rc, cols, False, device, codec)
+    nc = {"conn_key": np.asarray(s["key"]).astype(np.uint64), "idw": np.zeros(k, np.uint64),
+          "src": info[:, 0].astype(np.uint32), "dst": info[:, 1].astype(np.uint32), "sp": info[:, 2].astype(np.uint16),
+          "dp": info[:, 3].astype(np.uint16), "ack": info[:, 5].astype(np.uint32), "flag": info[:, 6].astype(np.uint8)}
+    h.create(offers_of(nc, list_form=True), list_form=True)
+    state0 = np.asarray(s["state0"])
+    assert np.array_equal(h.cols["seq"][:k], state0[:, 0].astype(np.uint32))
+    assert np.array_equal(h.cols["ack"][:k], state0[:, 1].astype(np.uint32))
+    return k
+
+
+def scenario_equivalence(rc, capacity, by_id, device, codec=None, n=1500, seed=0):
+    """Resolve -> create against the documented host procedure: demux of miss (conn_ref.first_missing), the rows
+    written by hand, the index and the pick index rebuilt, a second resolve: the same table, conn column and picks."""
+    rng = np.random.default_rng(capacity * 11 + by_id + seed)
+    cols = table(capacity, by_id, seed=seed)
+    nc = new_conns(rng, cols, by_id, max(1, min(n // 4, capacity // 2)))
+    b = batch_of(rng, cols, by_id, nc, n, known=0.4)
+    of = offers_of(nc)
+    h = Harness(rc, cols, by_id, device, codec)
+    ref, got = h.create(of, batch=b)
+    # the old path, by hand
+    old = Harness(rc, cols, by_id, device, codec)
+    tmap, _ = CR.table_map(cols["state"], cols["conn_key"], cols["id"] if by_id else None)
+    _c, _h, miss, _ = CR.resolve_ref(tmap, np.full(n, VALID, np.int8), b["conn_key"], id=b["id"] if by_id else None)
+    firsts = CR.first_missing(miss, b["conn_key"], b["id"] if by_id else None)
+    vac = np.nonzero((cols["state"] & LIVE) == 0)[0]
+    hand = {k: (None if v is None else v.copy()) for k, v in cols.items()}
+    for row, i in zip(vac.tolist(), firsts.tolist()):
+        o = int(b["which"][i])
+        hand["conn_key"][row] = b["conn_key"][i]
+        if by_id:
+            hand["id"].reshape(-1, 8)[row] = b["id"].reshape(-1, 8)[i]
+        for c in ("src", "dst", "sp", "dp", "flag"):
+            hand[c][row] = nc[c][o]
+        hand["seq"][row], hand["ack"][row] = (int(nc["ack"][o]) + 1) & 0xFFFFFFFF, (int(nc["ack"][o]) + 2) & 0xFFFFFFFF
+        hand["state"][row] = BORN
+    old.tab.load(**{k: v for k, v in hand.items() if v is not None})
+    old.cols = hand
+    old.rebuild()
+    for k, v in hand.items():
+        assert v is None or np.array_equal(v, h.cols[k]), k
+    key, idb = b["conn_key"], b["id"] if by_id else None
+    assert np.array_equal(old.resolve(key, idb), got["conn"])
+    pb, m = h.pick_batch()
+    P.compare(P.run_pick(rc, h.tab, m, device, codec, **pb), P.run_pick(rc, old.tab, m, device, codec, **pb), "old path")
+    return ref["n_new"]
+
+
+def scenario_sequences(rc, capacity, by_id, device, codec=None):
+    """Create -> close(REMOVE) -> create -> sweep -> create, rows being reused, the checkers after every step."""
+    rng = np.random.default_rng(capacity * 17 + by_id)
+    h = Harness(rc, table(capacity, by_id, seed=6), by_id, device, codec)
+    made = 0
+    for step in range(3):
+        vac = int(((h.cols["state"] & LIVE) == 0).sum())
+        nc = new_conns(rng, h.cols, by_id, max(1, min(vac, 40) + (2 if step == 1 else 0)))
+        nc["conn_key"] += np.uint64(step * 7919)
+        nc["src"] += np.uint32((step + 1) << 24)
+        r, _ = h.create(offers_of(nc), batch=batch_of(rng, h.cols, by_id, nc, 300, known=0.5))
+        made += r["n_new"]
+        if step == 0:
+            rows = np.concatenate([r["new_rows"][::2], rng.integers(0, capacity, capacity // 4 + 1).astype(np.uint32)])
+            h.close(close_rows=rows, remove=True)
+        elif step == 1:
+            live = np.nonzero(h.cols["state"] & LIVE)[0]
+            h.close(close_rows=live[::3].astype(np.uint32))  # killed, still in the table
+            h.close(sweep=True)
+    return made
+
+
+def scenario_moved(rc, capacity, by_id, sides):
+    """A table created on one side, copied to the other and continued there."""
+    rng = np.random.default_rng(capacity + 2 * by_id)
+    a = Harness(rc, table(capacity, by_id, seed=8), by_id, *sides[0])
+    nc = new_conns(rng, a.cols, by_id, 50)
+    r, _ = a.create(offers_of(nc), batch=batch_of(rng, a.cols, by_id, nc, 400))
+    b = a.moved(*sides[1])
+    b.check_lookups()
+    b.check_picks()
+    nc = new_conns(rng, b.cols, by_id, 30)
+    nc["conn_key"] += np.uint64(999331)
+    nc["src"] += np.uint32(0x05000000)
+    r2, _ = b.create(offers_of(nc), batch=batch_of(rng, b.cols, by_id, nc, 300))
+    return r["n_new"] + r2["n_new"]
+
+
+# ---- argument errors -------------------------------------------------------------------------------------------
+def check_einval(rc, device, codec=None):
+    """Every RSK_EINVAL case of the header; the table and the outputs stay untouched."""
+    lib = rc.lib()
+    by_id = True
+    h = Harness(rc, table(64, by_id, seed=1), by_id, device, codec)
+    tab = h.tab
+    dev = device
+    z = lambda k, dt=torch.int32: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
+    work = h.create_work(16, 8)
+    cols = {"src": z(8), "dst": z(8), "sp": z(8, torch.int16), "dp": z(8, torch.int16), "ack": z(8), "flag": z(8, torch.uint8),
+            "conn_key": z(8, torch.int64), "id": z(64, torch.uint8)}
+    n_offer = z(1)
+    pk = {"id": z(128, torch.uint8), "conn_key": z(16, torch.int64), "src": z(16), "dst": z(16), "sp": z(16, torch.int16),
+          "dp": z(16, torch.int16)}
+    outs = {"conn": z(16), "hit": z(16, torch.uint8), "miss": z(16, torch.int8), "n_miss": z(1), "new_rows": z(8),
+            "new_first": z(8), "new_offer": z(8), "offer_row": z(8), "n_new": z(1), "n_full": z(1), "n_refused": z(1)}
+    ad = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+
+    def call(n=16, flags=0, u_max=16, m_max=8, t=None, rows=None, ctx=True, cin=True, cout=True, wk=work, drop=(), pick=None,
+             over=None):
+        o = dict(cols)
+        p = dict(pk)
+        q = dict(outs)
+        for d in drop:
+            where, _, name = d.partition(":")
+            if name:
+                {"offer": o, "pkt": p, "out": q}[where][name] = None
+        for k, v in (over or {}).items():
+            where, _, name = k.partition(":")
+            {"offer": o, "pkt": p, "out": q}[where][name] = v
+        nof = n_offer if "n_offer" not in drop else None
+        offers = A.ConnOffers(ad(o["src"]), ad(o["dst"]), ad(o["sp"]), ad(o["dp"]), ad(o["ack"]), ad(o["flag"]),
+                              ad(o["conn_key"]), ad(o["id"]), ad(nof) if nof is not None else None, m_max)
+        ci = A.ConnCreateIn(ad(p["id"]), ad(p["conn_key"]), ad(p["src"]), ad(p["dst"]), ad(p["sp"]), ad(p["dp"]), offers,
+                            u_max, flags, 0, None, None, wk if isinstance(wk, (int, type(None))) else wk.data_ptr())
+        co = A.ConnCreateOut(ad(q["conn"]), ad(q["hit"]), ad(q["miss"]), ad(q["n_miss"]), ad(q["new_rows"]), ad(q["new_first"]),
+                             ad(q["new_offer"]), ad(q["offer_row"]), ad(q["n_new"]), ad(q["n_full"]), ad(q["n_refused"]),
+                             pick, None)
+        ta = tab.abi() if t is None else t
+        ra = tab.abi_create_rows() if rows is None else rows
+        pt = lambda x, on: ctypes.byref(x) if on else None  # noqa: E731
+        if codec is None:
+            return lib.rsk_conn_create_host(pt(ta, t is not False), pt(ra, rows is not False), n, pt(ci, cin), pt(co, cout), 1)
+        return lib.rsk_conn_create_batch(codec._ctx if ctx else None, pt(ta, t is not False), pt(ra, rows is not False), n,
+                                         pt(ci, cin), pt(co, cout), None)
+
+    LIST = A.CONN_CREATE_LIST
+    assert call() == 0 and call(n=0, flags=LIST, u_max=0) == 0
+    torch.cuda.synchronize() if codec is not None else None
+    before = {k: getattr(tab, k).clone() for k in ("state", "conn_key", "index", "pick")}
+    bad = []
+
+    def expect(what, **kw):
+        if call(**kw) != A.EINVAL:
+            bad.append(what)
+
+    if codec is not None:
+        expect("NULL ctx", ctx=False)
+    expect("NULL tab", t=False)
+    expect("NULL rows", rows=False)
+    expect("NULL in", cin=False)
+    expect("NULL out", cout=False)
+    expect("NULL work", wk=None)
+    for f in ("conn_key", "index", "id", "state", "src", "dst", "sp", "dp", "seq", "ack", "flag"):
+        t = tab.abi()
+        setattr(t, f, None)
+        expect("table without " + f, t=t)
+    for f in ("state", "conn_key", "id", "src", "dst", "sp", "dp", "seq", "ack", "flag"):
+        r = tab.abi_create_rows()
+        setattr(r, f, getattr(r, f) + 8)
+        expect("alias " + f, rows=r)
+    expect("u_max 0", u_max=0)
+    expect("m_max 0", m_max=0)
+    expect("u_max too large", u_max=(1 << 24) + 1)
+    expect("m_max too large", m_max=(1 << 21) + 1)
+    expect("unknown flags", flags=4)
+    for f in ("out:miss", "out:conn", "pkt:conn_key", "pkt:src", "pkt:dst", "pkt:sp", "pkt:dp", "pkt:id"):
+        expect("column form without " + f, drop=(f,))
+    expect("list form with n", flags=LIST)
+    expect("list form without conn_key", n=0, flags=LIST, drop=("offer:conn_key",))
+    expect("list form without id", n=0, flags=LIST, drop=("offer:id",))
+    for f in ("src", "dst", "sp", "dp", "ack", "flag"):
+        expect("offers without " + f, drop=("offer:" + f,))
+    expect("n_offer NULL", drop=("n_offer",))
+    for f in ("new_rows", "new_first", "new_offer"):
+        expect(f + " without n_new", drop=("out:n_new", "out:" + [x for x in ("new_rows", "new_first", "new_offer") if x != f][0],
+                                           "out:" + [x for x in ("new_rows", "new_first", "new_offer") if x != f][1]))
+    expect("REPEAT without offer_row", flags=A.CONN_CREATE_REPEAT, drop=("out:offer_row",))
+    expect("work not aligned", wk=work.data_ptr() + 4)
+    expect("pick not aligned", pick=tab.pick.data_ptr() + 4)
+    t = tab.abi()
+    t.index = t.index + 4
+    expect("index not aligned", t=t)
+    if codec is not None:  # the host twin reads the id columns bytewise
+        t, r = tab.abi(), tab.abi_create_rows()
+        t.id, r.id = t.id + 4, r.id + 4
+        expect("table ids not 8-B aligned", t=t, rows=r)
+        big = z(136, torch.uint8)
+        expect("packet ids not 8-B aligned", over={"pkt:id": big[4:132]})
+        expect("offer ids not 8-B aligned", n=0, flags=LIST, over={"offer:id": big[4:68]})
+    for cap in (0, (1 << 20) + 1):
+        t = tab.abi()
+        t.capacity = cap
+        expect(f"capacity {cap}", t=t)
+    t = tab.abi()
+    t.flags = 2
+    expect("unknown table flags", t=t)
+    expect("n too large", n=A.MAX_BATCH + 1)
+    assert not bad, bad
+    for k, v in before.items():
+        assert bool((getattr(tab, k) == v).all()), k
+    assert lib.rsk_conn_create_bytes(16, 0, 64, 0) == 0 and lib.rsk_conn_create_bytes(16, 8, 0, 0) == 0
+    assert lib.rsk_conn_create_bytes(16, 8, 64, 2) == 0 and lib.rsk_conn_create_bytes((1 << 24) + 1, 8, 64, 0) == 0
+    assert lib.rsk_conn_create_bytes(0, 8, 64, 1) % 16 == 0 and lib.rsk_conn_create_bytes(0, 8, 64, 1) > 0
+    return True

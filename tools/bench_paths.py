@@ -14,6 +14,8 @@ over 2^20 rows, each with and without the
 cur_in counts; IGroup::Flush over 2^20 rows) /
 conv_close_none / conv_close_rst / conv_close_timer_1m / conv_old_close / conv_old_close_1m (rsk_conv_close_batch
 with no reset hitting, with 1 % of the convs reset, behind the flush of 2^20 rows, and the index rebuild it replaces) /
+conn_create_none / _all / _1pct / conn_create_list_1m (+ _by_id) / conn_old_create_* (rsk_conn_create_batch: conns
+born on the device table against the demux + both builds + second resolve it replaces),
 conn_close_none / conn_close_rst / conn_close_timer_1m (+ _by_id) / conn_old_* (rsk_conn_close_batch with the pick
 index kept current: nothing marked, 1 % of the batch's conns reset and removed, a fifth of 2^20 rows timed out and
 removed, and the rsk_conn_index_build + rsk_conn_pick_build they replace) /
@@ -710,6 +712,118 @@ def main():
     torch.cuda.synchronize()
     assert cc_cnt.tolist()[:2] == [cc_rows["conn_close_rst"]["marked"]] * 2
     prep["conn_close_rst"]()
+    # conn create (rsk_conn_create_batch): conns born on the device table, both indexes kept current.  The table is the
+    # batch's own conns as one group (a client's flavour) and as groups of 10 (_by_id); a packet's 4-tuple and IdBuf
+    # are its conn's, one offer per conn.
+    #   conn_create_none(_by_id)   every conn LIVE, nothing missing: what keeping the call in the chain costs
+    #   conn_create_all(_by_id)    the table empty, every conn of the batch born in one call
+    #   conn_create_1pct(_by_id)   every 100th row vacant, its conn born again
+    #   conn_create_list_1m(_by_id) list form on 2^20 rows (one group / groups of 10), a fifth of them vacant
+    #   conn_old_create_*          the device share of the old path for the same outcome: the demux of miss,
+    #                              rsk_conn_index_build, rsk_conn_pick_build and the second resolve on the filled table
+    #                              (index and pick build alone for the list); the host round trip and its row writes
+    #                              are left out, which favours the old path
+    # state, both indexes and the packet columns are restored outside the timed span.
+    cn_row = torch.searchsorted(own_keys, ddec.conn_key).clamp(max=n_own - 1)
+    cn_tuple = lambda r: {"src": r.to(torch.int32), "dst": torch.full_like(r, 0x0A000001).to(torch.int32),  # noqa: E731
+                          "sp": (r % 60000 + 1024).to(torch.int16), "dp": (r // 60000 + 443).to(torch.int16)}
+    cn_pkt = cn_tuple(cn_row)
+    cn_idcol = ((cn_row % g_own + 1) * 0x100000001B3).view(torch.uint8)
+
+    def cn_offers(rows, tab=None):
+        """One offer per row of `rows` (the conn's tuple); with `tab` also the list form's key columns."""
+        o = cn_tuple(rows)
+        o.update(ack=torch.randint(0, 2**31, (rows.numel(),), device=dev, generator=gk, dtype=torch.int64).to(torch.int32),
+                 flag=torch.full((rows.numel(),), 0x18, dtype=torch.uint8, device=dev))
+        if tab is not None:
+            o["conn_key"] = tab.conn_key[rows].clone()
+            o["id"] = tab.id.view(-1, 8)[rows].reshape(-1).clone() if tab.by_id else None
+        return rc.ConnOffers(n_offer=torch.tensor([rows.numel()], dtype=torch.int32, device=dev), m_max=int(rows.numel()), **o)
+
+    def cn_table(src_tab, vacant=None):
+        """A copy of src_tab with the rows `vacant` (None: all) vacant, both indexes current, and what restores it."""
+        t = src_tab.to(dev)
+        if vacant is None:
+            t.state.zero_()
+        else:
+            t.state[vacant] = 0
+        t.rebuild(cx, stream=s)
+        t.rebuild_pick(cx, stream=s)
+        torch.cuda.synchronize()
+        return t, (t.state.clone(), t.index.clone(), t.pick.clone())
+
+    cn_cnt = torch.zeros(8, dtype=torch.int32, device=dev)  # n_miss, n_new, n_full, n_refused, pick_counts[2]
+    cn_new = {k: torch.empty(1 << 20, dtype=torch.int32, device=dev) for k in ("new_rows", "new_first", "new_offer")}
+    cn_cols = {k: (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev),
+                   torch.empty(n, dtype=torch.int8, device=dev)) for k in ("none", "all", "1pct")}
+    dmx_cn = rc.DemuxBuffers.alloc(n, dev)
+    cn_rows, cn_saved = {}, {}
+    for sfx, src_tab in (("", pk_own1), ("_by_id", pk_owng)):
+        idc = cn_idcol if src_tab.by_id else None
+        every = torch.arange(n_own, device=dev, dtype=torch.int64)
+        for case, vacant, offer_rows in (("none", every[:0], every), ("all", None, every), ("1pct", every[::100], every[::100])):
+            t, saved = cn_table(src_tab, vacant)
+            conn, hit, miss = (c.clone() for c in cn_cols[case])
+            cx.conn_resolve_batch(t, ddec.status, ddec.conn_key, conn, cmd=ddec.cmd, id=idc, hit=hit, miss=miss, stream=s)
+            torch.cuda.synchronize()
+            cols0 = (conn.clone(), hit.clone(), miss.clone())
+            offers = cn_offers(offer_rows)
+            work = t.create_work(n, offers.m_max)
+            name = f"conn_create_{case}{sfx}"
+
+            def op(t=t, offers=offers, work=work, conn=conn, hit=hit, miss=miss, idc=idc):
+                cx.conn_create_batch(t, offers, work, stream=s, u_max=n, conn_key=ddec.conn_key, id=idc, conn=conn, hit=hit,
+                                     miss=miss, n_miss=cn_cnt[0:1], n_new=cn_cnt[1:2], n_full=cn_cnt[2:3], n_refused=cn_cnt[3:4],
+                                     pick=True, pick_counts=cn_cnt[4:6], **cn_pkt, **cn_new)
+
+            def restore(t=t, saved=saved, cols=(conn, hit, miss), cols0=cols0):
+                t.state.copy_(saved[0]), t.index.copy_(saved[1]), t.pick.copy_(saved[2])
+                for c, c0 in zip(cols, cols0):
+                    c.copy_(c0)
+
+            ops[name] = op
+            if case != "none":
+                prep[name] = restore
+                miss0 = cols0[2]
+                full = cn_saved["full" + sfx]
+                ops[f"conn_old_create_{case}{sfx}"] = lambda miss0=miss0, full=full, idc=idc: (
+                    cx_cr.demux_batch(miss0, ddec.cmd, A.DEMUX_CONN_KEY | (A.DEMUX_ID if idc is not None else 0), dmx_cn,
+                                      conn_key=ddec.conn_key, id=idc, stream=s),
+                    cx.conn_index_build(full, stream=s), cx.conn_pick_build(full, stream=s),
+                    cx.conn_resolve_batch(full, ddec.status, ddec.conn_key, r_conn, cmd=ddec.cmd, id=idc, hit=r_hit, stream=s))
+            else:
+                cn_saved["full" + sfx] = t
+            op()
+            torch.cuda.synchronize()
+            # the conns born: the distinct keys of the missing packets (a conn whose packets are all control packets
+            # is never missed: C4 has some)
+            want_new = int(torch.unique(ddec.conn_key[cols0[2] == 1]).numel())
+            live = n_own - (n_own if vacant is None else int(vacant.numel())) + want_new
+            assert cn_cnt.tolist()[:4] == [0, want_new, 0, 0], (name, cn_cnt.tolist())
+            assert int((conn != -1).sum().item()) == looked and int((t.state & 1).sum().item()) == live, name
+            if case == "none":
+                assert want_new == 0 and torch.equal(t.index, saved[1]) and torch.equal(t.pick, saved[2])
+            else:
+                assert want_new > 0 and cn_cnt[5].item() == live and (cn_cnt[4].item() == 1 or src_tab.by_id), (name, cn_cnt.tolist())
+                restore()
+            cn_rows[name] = {"rows": n_own, "born": want_new, "missing_packets": int((cols0[2] == 1).sum().item()),
+                             "work_bytes": int(work.numel()) * 4}
+    cn_fifth = torch.arange(0, 1 << 20, 5, device=dev, dtype=torch.int64)
+    for sfx, src_tab in (("", pk_1m), ("_by_id", pk_1mg)):
+        t, saved = cn_table(src_tab, cn_fifth)
+        offers = cn_offers(cn_fifth, tab=t)
+        work = t.create_work(0, offers.m_max)
+        name = "conn_create_list_1m" + sfx
+        ops[name] = lambda t=t, offers=offers, work=work: cx.conn_create_batch(
+            t, offers, work, stream=s, list_form=True, n_new=cn_cnt[1:2], n_full=cn_cnt[2:3], n_refused=cn_cnt[3:4], pick=True,
+            pick_counts=cn_cnt[4:6], new_rows=cn_new["new_rows"], new_offer=cn_new["new_offer"])
+        prep[name] = cc_restore(t, saved)
+        ops[name]()
+        torch.cuda.synchronize()
+        assert cn_cnt.tolist()[1:6] == [cn_fifth.numel(), 0, 0, (1 << 20) // 10 if src_tab.by_id else 1, 1 << 20], (name, cn_cnt.tolist())
+        assert torch.equal(cn_new["new_rows"][:cn_fifth.numel()].to(torch.int64), cn_fifth)
+        prep[name]()
+        cn_rows[name] = {"rows": 1 << 20, "born": int(cn_fifth.numel()), "work_bytes": int(work.numel()) * 4}
     nseg =[int(dmx.n_seg.item()), int(dmx64.n_seg.item()), int(dmxs.n_seg.item()), int(dmxg.n_seg.item())]
     if args.only:
         keep = args.only.split(",")
@@ -806,6 +920,15 @@ def main():
     for k in ops:
         if k.startswith(("conn_close_", "conn_old_")):
             alg[k], items[k] = 1 + 4, (1 << 20) if "_1m" in k else cc_own.capacity
+    # conn create, per packet: miss read by the count; with packets missing also the key and the tuple (left as the
+    # figure for every row of the family); the list form per row of the table
+    for k in ops:
+        if k.startswith(("conn_create_", "conn_old_create_")):
+            alg[k] = 1 + 8 + 4
+            if "_1m" in k:
+                items[k] = 1 << 20
+            else:
+                items.pop(k, None)
     # pick: id (BY_ID) and the avoid key read, conn written; the build reads state (and id) and writes cand, pos
     for k in ops:
         if k.startswith("conn_pick_build"):
@@ -888,6 +1011,20 @@ def main():
                 res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
         if "conn_close_none" in out and "conv_close_none" in out:
             res["conn_close_none_over_conv_close_none"] = round(out["conn_close_none"]["ms"] / out["conv_close_none"]["ms"], 3)
+    if any(k.startswith("conn_create_") for k in out):
+        res["conn_create_rows"] = {k: v for k, v in cn_rows.items() if k in out}
+        for k in [k for k in out if k.startswith("conn_create_")]:
+            tail = k[len("conn_create_"):]
+            y = "conn_old_timer_1m" + tail[len("list_1m"):] if tail.startswith("list_1m") else "conn_old_create_" + tail
+            if y in out:
+                res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
+        for y in ("conn_close_none", "conn_resolve"):
+            for k in ("conn_create_none", "conn_create_none_by_id"):
+                if k in out and y in out:
+                    res[f"{k}_over_{y}"] = round(out[k]["ms"] / out[y]["ms"], 3)
+        res["rounds"], res["reps"] = args.rounds, args.reps
+        res["ms_rounds"] = {k: [round(x, 4) for x in times[k]] for k in out
+                            if k.startswith(("conn_create_", "conn_old_", "conn_close_none", "conn_resolve"))}
     picks = [k for k in out if k.startswith("conn_pick_")]
     if picks:
         res["conn_pick_rows"] = {"client": 10, "server": [64, 10], "own_one": n_own, "own_groups": [g_own, 10],
