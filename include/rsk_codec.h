@@ -1096,8 +1096,15 @@ int rsk_conn_close_host(const rsk_conn_table *tab, const rsk_conn_rows *rows, co
  * (TcpAckPool): a caller-owned device list of m_max entries, the first min(*n_offer, m_max) in use (*n_offer is a
  * device word).  An offer has src, dst, sp, dp in the orientation of the parse's TcpInfo of a DATA packet of the
  * connection (the one FakeTcp is constructed with and the row stores), ack (the info.ack Wait2TransferInfo
- * leaves) and flag; no seq (FakeTcp::Init never reads it).  It is matched by its 4-tuple alone
+ * leaves: the ack of the pooled record, which on a server is the th_seq of its own SYN|ACK, RawTcp.cpp:221-227)
+ * and flag; no seq (FakeTcp::Init never reads it).  flag is the flag the conn SENDS with, not
+ * the handshake's: the reference builds the conn's TcpInfo from the DATA packet's ConnInfo (server/SNetGroup.cpp:25,
+ * bean/TcpInfo.cpp:55-58), Wait2TransferInfo transfers seq and ack only (net/TcpAckPool.cpp:45-53), so it is the
+ * member default TH_ACK (bean/TcpInfo.h:15); an offer that carried the SYN row's flag would put SYN on every
+ * packet of the conn.  It is matched by its 4-tuple alone
  * (TcpCmpFn keys both pools by src, sp, dst, dp); of two offers with one tuple the lower index is the tuple's.
+ * What the host keeps around the call (the first handshake of a tuple wins, a refusal empties the tuple's pool
+ * entries) is INTEGRATION.md's; tests/golden/conncreate.npz holds call and procedure to the reference's classes.
  * COLUMN FORM (flags without RSK_CONN_CREATE_LIST), behind rsk_conn_resolve_batch whose conn / hit / miss / n_miss
  * it continues; miss must be the resolve's (or an earlier call's) for the table as it is:
  *   1. The considered packets are the first u_max packets with miss[i] == RSK_RECV_VALID, in packet order; no

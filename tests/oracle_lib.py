@@ -17,6 +17,7 @@ REF_PARSE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_parse.so")
 REF_DEMUX_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_demux.so")
 REF_CONTROL_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_control.so")
 REF_TCPSTATE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_tcpstate.so")
+REF_CONNCREATE_SO = os.path.join(ROOT, "oracle", "_ref", "librsk_ref_conncreate.so")
 
 _vp = ctypes.c_void_p
 
@@ -631,6 +632,127 @@ class RefTcpState:
         if self.h:
             self.L.ref_ts_close(self.h)
             self.h = None
+
+
+class RefConnCreate:
+    """The reference's own way from a handshake to a fake-TCP conn (oracle/_ref/librsk_ref_conncreate.so: RawTcp,
+    TcpAckPool, ServerNetManager, SNetGroup, INetGroup, FakeTcp compiled from /root/reference;
+    oracle/ref_conncreate_harness.cpp).  RTLD_LAZY as RefParse.  One object is one TcpAckPool, one ServerNetManager
+    over it, G SNetGroups and a client group; every packet is an Ethernet capture."""
+
+    NOT_DELIVERED = -2**31
+
+    def __init__(self, n_groups: int, persist_ms: int, path: str = REF_CONNCREATE_SO):
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        L = self.L = ctypes.CDLL(path, mode=os.RTLD_LAZY)
+        u32, u64, i = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+        L.ref_cc_open.restype = _vp
+        L.ref_cc_open.argtypes = [u32, u64]
+        L.ref_cc_syn.argtypes = [_vp, u32, _vp, _vp, _vp, i, u64, _vp]
+        L.ref_cc_accept.argtypes = [_vp, u32, _vp, u64]
+        L.ref_cc_data.argtypes = [_vp, u32] + [_vp] * 10
+        L.ref_cc_flush.argtypes = [_vp, i, u64]
+        L.ref_cc_send.argtypes = [_vp, u32, u32, _vp, u32, _vp, _vp]
+        L.ref_cc_pools.argtypes = [_vp, u32] + [_vp] * 7
+        L.ref_cc_conns.argtypes = [_vp, u32] + [_vp] * 5
+        L.ref_cc_dial.argtypes = [_vp, u32, _vp, u32, _vp, _vp, _vp, _vp]
+        L.ref_cc_close.argtypes = [_vp]
+        L.ref_cc_close.restype = None
+        self.h = L.ref_cc_open(n_groups, persist_ms)
+
+    @staticmethod
+    def _arena(pkts):
+        """-> (arena with slack behind the last packet, offsets, lengths); the reference reads headers without
+        looking at caplen."""
+        off = np.cumsum([0] + [len(p) for p in pkts[:-1]]).astype(np.uint64) if pkts else np.zeros(0, np.uint64)
+        arena = np.frombuffer(b"".join(pkts) + bytes(128), np.uint8).copy()
+        return arena, off, np.array([len(p) for p in pkts], np.uint32)
+
+    def syn(self, pkts, ts: int, server: bool = True) -> np.ndarray:
+        """SYN captures through RawTcp::RawInput; -> took [k]: the ack pool stamped an entry."""
+        arena, off, ln = self._arena(pkts)
+        took = np.zeros(len(pkts), np.uint8)
+        rc = self.L.ref_cc_syn(self.h, len(pkts), _p(arena), _p(off), _p(ln), int(server), ts, _p(took))
+        assert rc == 0, rc
+        return took
+
+    def accept(self, tuples, ts: int) -> None:
+        """tuples [k, 4] = src, dst, sp, dp as GetTcpInfo gives them on the server, into ServerNetManager::mPool."""
+        t = np.ascontiguousarray(np.asarray(tuples, np.uint32).reshape(-1, 4))
+        rc = self.L.ref_cc_accept(self.h, len(t), _p(t), ts)
+        assert rc == 0, rc
+
+    def data(self, pkts, group, key) -> dict:
+        """DATA captures through RawInput and INetGroup::Input of groups[group[i]] with a head carrying key[i]."""
+        n = len(pkts)
+        arena, off, ln = self._arena(pkts)
+        group = np.ascontiguousarray(np.asarray(group, np.uint32))
+        key = np.ascontiguousarray(np.asarray(key, np.uint64))
+        assert len(group) == len(key) == n
+        ret, created = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        conn, ack, info = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros((n, 7), np.uint32)
+        rc = self.L.ref_cc_data(self.h, n, _p(arena), _p(off), _p(ln), _p(group), _p(key), _p(ret), _p(created), _p(conn),
+                                _p(ack), _p(info))
+        assert rc == 0, rc
+        return {"ret": ret, "created": created, "conn": conn, "ack": ack, "info": info}
+
+    def flush(self, which: int, ts: int) -> None:
+        """which 0: TcpAckPool::OnFlush(ts); 1: ServerNetManager::OnFlush(ts)."""
+        rc = self.L.ref_cc_flush(self.h, which, ts)
+        assert rc == 0, rc
+
+    def send(self, group: int, draws) -> dict:
+        """len(draws) sends through INetGroup::Send of one group, which must consume one draw each (every conn
+        alive); -> sender keys and the draws each send took."""
+        draws = np.ascontiguousarray(np.asarray(draws, np.uint32))
+        n = len(draws)
+        sender, consumed = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        rc = self.L.ref_cc_send(self.h, group, n, _p(draws), n, _p(sender), _p(consumed))
+        assert rc == 0, rc
+        return {"sender": sender, "consumed": consumed}
+
+    def pools(self, cap: int = 1 << 14) -> dict:
+        """Both pools in their maps' order: ack [n, 6] = src, dst, sp, dp, seq, ack with ack_exp [n]; net [m, 4] with
+        net_exp [m]; closed = the accepted sockets closed so far."""
+        ack, ae, na = np.zeros((cap, 6), np.uint32), np.zeros(cap, np.uint64), np.zeros(1, np.uint32)
+        net, ne, nn = np.zeros((cap, 4), np.uint32), np.zeros(cap, np.uint64), np.zeros(1, np.uint32)
+        closed = np.zeros(1, np.uint32)
+        rc = self.L.ref_cc_pools(self.h, cap, _p(ack), _p(ae), _p(na), _p(net), _p(ne), _p(nn), _p(closed))
+        assert rc == 0, rc
+        a, m = int(na[0]), int(nn[0])
+        return {"ack": ack[:a].copy(), "ack_exp": ae[:a].copy(), "net": net[:m].copy(), "net_exp": ne[:m].copy(),
+                "closed": int(closed[0])}
+
+    def conns(self, cap: int = 1 << 14) -> dict:
+        """The conns made so far in creation order: group, key, the packet (index in its batch) and mInfo after
+        Init [n, 7] = src, dst, sp, dp, seq, ack, flag."""
+        n = np.zeros(1, np.uint32)
+        group, key = np.zeros(cap, np.int32), np.zeros(cap, np.uint64)
+        packet, info = np.zeros(cap, np.uint32), np.zeros((cap, 7), np.uint32)
+        rc = self.L.ref_cc_conns(self.h, cap, _p(n), _p(group), _p(key), _p(packet), _p(info))
+        assert rc == 0, rc
+        k = int(n[0])
+        return {"group": group[:k].copy(), "key": key[:k].copy(), "packet": packet[:k].copy(), "info": info[:k].copy()}
+
+    def dial(self, tuples, wait_ms: int = 1) -> dict:
+        """The statement sequence of ClientNetManager::createINetConn per tuple [k, 4] (src = the local end)."""
+        t = np.ascontiguousarray(np.asarray(tuples, np.uint32).reshape(-1, 4))
+        k = len(t)
+        ok, key = np.zeros(k, np.uint8), np.zeros(k, np.uint64)
+        info, found = np.zeros((k, 7), np.uint32), np.zeros(k, np.uint8)
+        rc = self.L.ref_cc_dial(self.h, k, _p(t), wait_ms, _p(ok), _p(key), _p(info), _p(found))
+        assert rc == 0, rc
+        return {"ok": ok, "key": key, "info": info, "found": found}
+
+    def close(self):
+        if self.h:
+            self.L.ref_cc_close(self.h)
+            self.h = None
+
+
+def ref_conncreate_available() -> bool:
+    return os.path.exists(REF_CONNCREATE_SO)
 
 
 def ref_tcpstate_available() -> bool:
