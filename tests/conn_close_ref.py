@@ -23,6 +23,7 @@ from tests import conn_ref as CR
 from tests import control_golden as G
 from tests import control_ref as C
 from tests import pick_ref as P
+from tests.collide import group_home
 
 NONE = A.CONN_NONE
 NO_RST = 0xFFFFFFFF
@@ -85,6 +86,7 @@ class Harness:
         self.tab = P.make_table(rc, cols, by_id, device, codec)
         self.work = self.tab.close_work()
         self.killed, self.removed = set(), set()
+        self.keep_index = False
         self.sync()
 
     def moved(self, device, codec=None):
@@ -96,6 +98,7 @@ class Harness:
         h.tab = self.tab.to(device)
         h.work = h.tab.close_work()
         h.killed, h.removed = set(self.killed), set(self.removed)
+        h.keep_index = False
         return h
 
     def sync(self):
@@ -208,10 +211,19 @@ class Harness:
         want = CR.resolve_ref(tmap, np.ones(len(key), np.int8), key, id=idb)[0]
         got = self.resolve(key, idb)
         assert np.array_equal(got, want), ("index as left", np.nonzero(got != want)[0][:8])
+        self.check_index("index as left")
+        if self.keep_index:  # the scenario goes on with the index as the call left it
+            return
         self.tab.rebuild(self.codec)
         self.sync()
         got = self.resolve(key, idb)
         assert np.array_equal(got, want), ("index rebuilt", np.nonzero(got != want)[0][:8])
+        self.check_index("index rebuilt")
+
+    def check_index(self, what):
+        """rsk_conn.h's contract on the index as it stands (tests/collide.index_invariant), up to 4097 rows."""
+        if self.cap <= 4097:
+            CR.check_index(self.tab, self.cols, self.by_id, what=what)
 
     # -- picks ----------------------------------------------------------------------------------------------
     def pick_batch(self):
@@ -409,25 +421,6 @@ def scenario_sequences(rc, capacity, by_id, device, codec=None):
 
 
 # ---- scenario 4b: an emptied group must not cut other ids' probe chains ------------------------------------------
-M64 = 2**64 - 1
-
-
-def _mix(x):
-    x ^= x >> 30
-    x = x * 0xBF58476D1CE4E5B9 & M64
-    x ^= x >> 27
-    x = x * 0x94D049BB133111EB & M64
-    return x ^ (x >> 31)
-
-
-def group_home(idw, capacity):
-    """rsk_conn.h's conn_home(0, id, conn_slots(capacity)): where the probe for an IdBuf's group starts."""
-    slots = 4
-    while slots < 2 * capacity:
-        slots <<= 1
-    return (_mix(_mix((idw + 0x9E3779B97F4A7C15) & M64)) >> 32) & (slots - 1)
-
-
 def scenario_probe_chains(rc, capacity, device, codec=None):
     """Every row its own group.  Two ids that share a home: the one placed later probes past the other's entry,
     whichever that is, so closing each half of the rows in turn (on a fresh table) makes a surviving id probe past
@@ -447,6 +440,60 @@ def scenario_probe_chains(rc, capacity, device, codec=None):
         assert len(ref["marked_rows"]) == len(range(half, capacity, 2))
         h.close(close_rows=np.arange(half, capacity, 4, dtype=np.uint32), remove=True)  # emptied entries are met again
     return split
+
+
+# ---- scenario 4c: constructed clusters (tests/collide.py) ---------------------------------------------------------
+COLLIDE_LENGTHS = CR.CLUSTER_LENGTHS  # the close runs on a full table: the run is as long as the table has rows
+
+
+def collide_table(capacity, by_id, home, groups=7, live=None):
+    """`live` rows (default: half of them) UP in random places, every key probing from `home`; BY_ID: over `groups`
+    IdBufs whose group entries in the pick index probe from `home` too.  -> (cols, the groups' id words)."""
+    from tests import collide as X
+
+    rng = np.random.default_rng(capacity * 2 + by_id)
+    cols = CR.random_columns(rng, capacity, by_id=by_id)
+    rows = np.sort(rng.permutation(capacity)[: capacity // 2 if live is None else live])
+    gids = X.ids_at(home, groups) if by_id else np.zeros(1, np.uint64)
+    idw = gids[np.concatenate([np.arange(len(gids)), rng.integers(0, len(gids), len(rows))])[: len(rows)]]
+    CR.place(cols, rows, X.keys_at(home, len(rows), idw), id=P.id_bytes(idw) if by_id else None)
+    return cols, gids
+
+
+def check_clusters(h, home, run):
+    """The read-back proof that a harness's table is what the scenario says: the conn index one run of `run` entries
+    from `home`, and (BY_ID, on a pick index that was just built) the groups' entries one run from `home` too."""
+    from tests import collide as X
+
+    X.one_run(h.tab.index.cpu().numpy(), home, run)
+    if h.by_id:
+        P.check_group_run(h.tab, h.cols, home)
+
+
+def scenario_collide_close(rc, length, by_id, wrap, device, codec=None):
+    """A full table of `length` rows that is ONE run of the index: every second row closed without and with REMOVE,
+    then the rest; BY_ID: the groups of one pick home emptied one by one, so the groups behind them in the chain are
+    picked past emptied entries."""
+    from tests import collide as X
+
+    home = CR.WRAP_HOME if wrap else CR.INNER_HOME
+    cols, gids = collide_table(length, by_id, home, groups=9, live=length)
+    live = np.arange(length)
+    for remove in (False, True):
+        h = Harness(rc, cols, by_id, device, codec)
+        check_clusters(h, home, length)
+        h.close(close_rows=live[0::2].astype(np.uint32), remove=remove)
+        X.one_run(h.tab.index.cpu().numpy(), home, length - (len(live[0::2]) if remove else 0))
+        h.close(close_rows=live[1::2].astype(np.uint32), remove=remove)
+        h.close(sweep=True)
+        assert not (h.cols["state"] & LIVE).any()
+    if by_id:
+        h = Harness(rc, cols, True, device, codec)
+        w = CR.id_words(cols["id"], length)
+        for j, g in enumerate(gids[::2].tolist() + gids[1::2].tolist()):
+            h.close(close_rows=np.nonzero(w == np.uint64(g))[0].astype(np.uint32), remove=bool(j % 2))
+        assert not ((h.cols["state"] & UP) == UP).any()
+    return length
 
 
 # ---- scenario 5: the reference's recorded control walk ---------------------------------------------------------

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from rsock_amd import _abi as A
+from tests import collide as X
 from tests import conn_close_ref as K
 from tests import conn_ref as CR
 from tests import pick_ref as P
@@ -772,3 +773,87 @@ def check_einval(rc, device, codec=None):
     assert lib.rsk_conn_create_bytes(16, 8, 64, 2) == 0 and lib.rsk_conn_create_bytes((1 << 24) + 1, 8, 64, 0) == 0
     assert lib.rsk_conn_create_bytes(0, 8, 64, 1) % 16 == 0 and lib.rsk_conn_create_bytes(0, 8, 64, 1) > 0
     return True
+
+
+# ---- constructed clusters (tests/collide.py) -------------------------------------------------------------------
+# (rows, LIVE rows at the start, new conns of the column-form call): tables that the calls fill, so the run of the index
+# ends as long as the table has rows, at the lengths of conn_ref.CLUSTER_LENGTHS; and 63 / 64 / 65 lanes of the insert
+# launch racing for a run that 64 rows hold already
+COLLIDE_CASES = tuple((n, n // 8, None) for n in CR.CLUSTER_LENGTHS) + ((257, 64, 63), (257, 64, 64), (257, 64, 65))
+
+
+def collide_conns(rng, k, home, idw, salt):
+    """k conns nobody knows: keys (under their id words) and 4-tuples (the offers hash) all probing from `home`."""
+    from tests import collide as X
+
+    src, dst, sp, dp = X.tuples_at(home, k, salt=salt)
+    return {"conn_key": X.keys_at(home, k, idw, salt=salt), "idw": np.asarray(idw, np.uint64).copy(), "src": src, "dst": dst,
+            "sp": sp, "dp": dp, "ack": rng.integers(0, 2**32, k).astype(np.uint32), "flag": rng.integers(0, 256, k).astype(np.uint8)}
+
+
+def scenario_collide(rc, capacity, live0, k, by_id, wrap, device, codec=None, new_groups=5):
+    """Table keys, new keys, their 4-tuples and (BY_ID) the old and new groups' ids all probe from one entry, so the
+    index, the call's dedup table, its offers table and the pick's group entries are one run each, across the end of
+    the table when `wrap`.  `live0` rows are LIVE; a batch of 3 x capacity packets with several packets per new key
+    makes k conns (default: all but capacity / 16 of the vacant rows), the list form the rest, so the run ends as
+    long as the table has rows.  Then every row of the first call is removed and the same conns are created again,
+    in place, in the index AS THE CLOSE LEFT IT (the harness's rebuild is held back until that create is checked).
+    Every checker of the harness runs after each call (tests/collide.index_invariant among them)."""
+    home = CR.WRAP_HOME if wrap else CR.INNER_HOME
+    rng = np.random.default_rng(capacity * 4 + by_id * 2 + wrap)
+    cols, gids = K.collide_table(capacity, by_id, home, live=live0)
+    h = Harness(rc, cols, by_id, device, codec)
+    K.check_clusters(h, home, live0)  # the proof that the table is one cluster
+    vac = capacity - live0
+    k_list = max(vac // 16, 1) if k is None else 4
+    k = vac - k_list if k is None else k
+    fresh = X.ids_at(home, new_groups, salt=1) if by_id else np.zeros(1, np.uint64)
+    pool = np.concatenate([gids, fresh]) if by_id else fresh
+    ids = pool[rng.integers(0, len(pool), k)]
+    if by_id:
+        ids[:new_groups] = fresh  # every new group is born
+    nc = collide_conns(rng, k, home, ids, salt=2)
+    b = batch_of(rng, cols, by_id, nc, 3 * capacity, known=0.3)
+    r, _ = h.create(offers_of(nc), batch=b)
+    assert r["n_new"] == k and r["n_miss"] == 0
+    X.one_run(h.tab.index.cpu().numpy(), home, live0 + k)
+    nl = collide_conns(rng, k_list, home, pool[rng.integers(0, len(pool), k_list)], salt=3)
+    r, _ = h.create(offers_of(nl, list_form=True), list_form=True)
+    assert r["n_new"] == k_list
+    X.one_run(h.tab.index.cpu().numpy(), home, live0 + k + k_list)
+    # create -> close (remove) -> create: the in-place inserts land in the run as the close rebuilt it
+    made = np.nonzero(np.isin(h.cols["conn_key"], nc["conn_key"]) & ((h.cols["state"] & LIVE) != 0))[0]
+    assert len(made) == k
+    h.keep_index = True
+    h.close(close_rows=rng.permutation(made).astype(np.uint32), remove=True)
+    h.keep_index = False
+    X.one_run(h.tab.index.cpu().numpy(), home, live0 + k_list)
+    r, _ = h.create(offers_of(nc), batch=batch_of(rng, h.cols, by_id, nc, 4 * capacity, known=0.3))
+    assert r["n_new"] == k
+    X.one_run(h.tab.index.cpu().numpy(), home, live0 + k + k_list)
+    return k + k_list + k
+
+
+def scenario_collide_groups(rc, capacity, device, codec=None, groups=70):
+    """More than 64 new groups whose entries in the pick index probe from one entry, born in one call next to 7 old
+    ones of the same entry; then every second new group emptied, and conns of emptied and of further new groups born."""
+    from tests import collide as X
+
+    home = CR.WRAP_HOME
+    rng = np.random.default_rng(capacity + groups)
+    cols, gids = K.collide_table(capacity, True, home)
+    h = Harness(rc, cols, True, device, codec)
+    K.check_clusters(h, home, capacity // 2)
+    fresh = X.ids_at(home, groups + 10, salt=1)
+    ids = np.concatenate([fresh[:groups], gids, fresh[rng.integers(0, groups, 20)]])
+    nc = collide_conns(rng, len(ids), home, ids, salt=2)
+    r, _ = h.create(offers_of(nc), batch=batch_of(rng, cols, True, nc, 3 * len(ids), known=0.2))
+    assert r["n_new"] == len(ids)
+    w = CR.id_words(h.cols["id"], capacity)
+    gone = np.nonzero(np.isin(w, fresh[:groups:2]) & ((h.cols["state"] & LIVE) != 0))[0]
+    h.close(close_rows=gone.astype(np.uint32), remove=True)
+    ids = np.concatenate([fresh[:groups:4], fresh[groups:]])
+    nc = collide_conns(rng, len(ids), home, ids, salt=3)
+    r, _ = h.create(offers_of(nc, list_form=True), list_form=True)
+    assert r["n_new"] == len(ids)
+    return groups

@@ -200,3 +200,103 @@ def edge_table(by_id):
         pid = np.concatenate([idb] * 5 + [flip.ravel()])
         pk = np.concatenate([pk, keys])
     return cols, cap, (pk, pid)
+
+
+# ---- constructed clusters (tests/collide.py) -------------------------------------------------------------------
+# one run of the index as long as the table has rows, at the wave's edges, past one block of the build and the
+# resolve; 2049 once per table kind
+CLUSTER_LENGTHS = (63, 64, 65, 257, 1025)
+CLUSTER_SHAPES = ("one_home", "two_homes", "duplicates")
+CLUSTER_SHAPES_BY_ID = CLUSTER_SHAPES + ("one_key_many_ids",)
+WRAP_HOME, INNER_HOME = -3, 5  # entry slots - 3 (the run crosses the table's end) and entry 5 (it does not)
+
+
+def cluster_table(length, shape, by_id, wrap):
+    """Every row UP, capacity = length, every key's probe starting at one entry H (two_homes: at H and H + 1 in
+    turn), the rows in random order.  -> (cols, H, distinct keys, probes (conn_key, id words)): every present key,
+    absent keys of the same home (their probe walks the whole run to the free entry behind it), of the
+    neighbouring homes, and of an entry inside the run."""
+    from tests import collide as X
+
+    cap, home = length, (WRAP_HOME if wrap else INNER_HOME)
+    rng = np.random.default_rng(length * 8 + by_id * 4 + wrap * 2 + CLUSTER_SHAPES_BY_ID.index(shape))
+    cols = random_columns(rng, cap, by_id=by_id)
+    id0 = 0x0123456789ABCDEF if by_id else 0
+    ids = np.full(cap, id0, np.uint64)
+    if shape == "one_key_many_ids":
+        keys = np.full(cap, 0x10002711_9C40, np.uint64)
+        ids = X.ids_at(home, cap, key=int(keys[0]))
+    elif shape == "two_homes":
+        keys = np.empty(cap, np.uint64)
+        keys[0::2] = X.keys_at(home, (cap + 1) // 2, id0)
+        keys[1::2] = X.keys_at(home + 1, cap // 2, id0, salt=1)
+    else:
+        keys = X.keys_at(home, cap, id0)
+        if shape == "duplicates":  # a third of the rows repeat a key of the cluster
+            rep = rng.permutation(cap)[: cap // 3]
+            keys[rep] = keys[rng.integers(0, cap, len(rep))]
+    order = rng.permutation(cap)
+    keys, ids = keys[order], ids[order]
+    place(cols, np.arange(cap), keys, id=ids.view(np.uint8) if by_id else None)
+    distinct = len({(int(i), int(k)) for i, k in zip(ids, keys)})
+    pk = [keys, X.keys_at(home, 8, id0, salt=7), X.keys_at(home - 1, 3, id0, salt=8), X.keys_at(home + 1, 3, id0, salt=9),
+          X.keys_at(home + 2, 3, id0, salt=10), X.keys_at(home + cap - 1, 3, id0, salt=11), X.keys_at(home + cap, 3, id0, salt=12)]
+    pi = [ids] + [np.full(len(k), id0, np.uint64) for k in pk[1:]]
+    if by_id:  # a present key under an absent id of the same home, and under the neighbour's
+        pk += [keys[:4], keys[:4]]
+        pi += [X.ids_at(home, 4, salt=13, key=int(keys[0])), X.ids_at(home + 1, 4, salt=14, key=int(keys[0]))]
+    return cols, home, distinct, (np.concatenate(pk), np.concatenate(pi))
+
+
+def built_table(rc, cols, by_id, device, codec=None):
+    """-> (ConnTable on `device` with its index built there, n_dup)."""
+    import torch
+
+    tab = make_table(rc, cols, len(cols["state"]), device, by_id=by_id)
+    nd = torch.full((1,), -1, dtype=torch.int32, device=device)
+    tab.rebuild(codec, n_dup=nd)
+    if codec is not None:
+        torch.cuda.synchronize()
+    return tab, int(nd.cpu().numpy().view(np.uint32)[0])
+
+
+def resolve_on(rc, tab, key, idb, device, codec=None):
+    """The conn column of a resolve of all-VALID DATA packets, on the host twin or the device."""
+    import torch
+
+    status = np.ones(len(key), np.int8)
+    if codec is None:
+        return rc.conn_resolve_host(tab, status, key, id=idb)[0]
+    t = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(device)  # noqa: E731
+    conn = torch.zeros(len(key), dtype=torch.int32, device=device)
+    codec.conn_resolve_batch(tab, t(status, np.int8), t(key, np.int64), conn, id=t(idb, np.uint8))
+    torch.cuda.synchronize()
+    return conn.cpu().numpy().view(np.uint32)
+
+
+def check_index(tab, cols, by_id, what=""):
+    """collide.index_invariant on the table's index as it stands."""
+    from tests import collide as X
+
+    cap = len(cols["state"])
+    return X.index_invariant(tab.index.cpu().numpy(), cap, cols["state"], cols["conn_key"],
+                             id_words(cols["id"], cap) if by_id else None, by_id, what=what)
+
+
+def scenario_cluster(rc, length, shape, by_id, wrap, device, codec=None):
+    """Build and resolve on a table that is one cluster: n_dup, the proof that the keys are one run from the
+    predicted home, the index's contract, and every lookup against resolve_ref."""
+    from tests import collide as X
+
+    cols, home, distinct, (pk, pi) = cluster_table(length, shape, by_id, wrap)
+    tab, ndup = built_table(rc, cols, by_id, device, codec)
+    assert ndup == length - distinct, (ndup, length, distinct)
+    X.one_run(tab.index.cpu().numpy(), home, distinct)
+    assert check_index(tab, cols, by_id) == distinct
+    tmap, _ = table_map(cols["state"], cols["conn_key"], cols["id"] if by_id else None)
+    idb = pi.view(np.uint8) if by_id else None
+    want = resolve_ref(tmap, np.ones(len(pk), np.int8), pk, id=idb)[0]
+    got = resolve_on(rc, tab, pk, idb, device, codec)
+    assert np.array_equal(got, want), np.nonzero(got != want)[0][:8]
+    assert bool((want[:length] != NONE).all()) and bool((want[length:] == NONE).all())
+    return distinct

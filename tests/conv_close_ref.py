@@ -164,7 +164,9 @@ def compare(got, want):
 
 def check_lookups(rc, tab, cols, lookup_state, by_dst, by_id, device, codec=None):
     """The key of every row that is LIVE in `cols` resolves, on the index as it stands, to what a rebuild over
-    `lookup_state` gives: the key's lowest row that stays, or unknown."""
+    `lookup_state` gives: the key's lowest row that stays, or unknown; the index itself is a build's over
+    `lookup_state` (rsk_conn.h's contract; under HOLD it forgets rows that stay LIVE)."""
+    R.check_index(tab, cols, by_dst, by_id, live=(lookup_state & LIVE) != 0, what="index as it stands")
     live = np.nonzero(cols["state"] & LIVE)[0]
     if len(live) == 0:
         return
@@ -775,3 +777,181 @@ def check_einval(rc, device, codec=None):
     assert L.rsk_conv_close_bytes(0) == 0 and L.rsk_conv_close_bytes(A.CONN_MAX_ROWS + 1) == 0
     for cap in (1, 15, 16, 17, 1025, A.CONN_MAX_ROWS):  # one mark per row, rounded up to 16
         assert L.rsk_conv_close_bytes(cap) == (cap + 15) // 16 * 16
+
+
+# ---- constructed clusters (tests/collide.py): index, resolve, create and close on one run ---------------------------
+CLUSTER_LENGTHS = R.CR.CLUSTER_LENGTHS
+INDEX_CLUSTERS = ([(n, shape, f, True) for n in CLUSTER_LENGTHS for shape in R.CR.CLUSTER_SHAPES for f in R.FLAG_COMBOS] +
+                  [(65, "two_homes", (True, True), False), (257, "duplicates", (False, False), False),
+                   (1025, "one_home", (False, True), False), (2049, "one_home", (True, True), True),
+                   (2049, "duplicates", (True, False), True)])
+LIFE_CLUSTERS = ([(n, f, True) for n in CLUSTER_LENGTHS for f in R.FLAG_COMBOS] +
+                 [(65, (True, True), False), (257, (False, False), False), (1025, (True, False), False), (2049, (True, True), True)])
+
+
+def cluster_keys(k, by_dst, by_id, home, slots, salt=0, base=0):
+    """k distinct conv-table keys whose probes all start at `home`: the client's 32-bit convs by search, the others
+    by running the hash backwards (BY_DST: the 64-bit key word is dst << 32 | conv; BY_ID alone: every conv under an
+    IdBuf of its own; both: three IdBufs).  Another `salt`, other keys (the client's: the keys after the first `base`).  -> dict(conv, dst, id [k*8]) with None for
+    the absent columns."""
+    from tests import collide as X
+
+    if not by_dst and not by_id:
+        return {"conv": X.convs_at(home, base + k, slots)[base:], "dst": None, "id": None}
+    if not by_dst:
+        conv = ((np.arange(1, k + 1, dtype=np.uint64) + np.uint64(salt << 16)) * np.uint64(2654435761)).astype(np.uint32)
+        return {"conv": conv, "dst": None, "id": X.ids_at(home, k, salt=salt, key=conv.astype(np.uint64)).view(np.uint8)}
+    idw = np.array([0x1111, 0x0123456789ABCDEF, 2**64 - 1], np.uint64)[np.arange(k) % 3] if by_id else np.zeros(k, np.uint64)
+    key = X.keys_at(home, k, idw, salt=salt)
+    return {"conv": key.astype(np.uint32), "dst": (key >> np.uint64(32)).astype(np.uint32), "id": idw.view(np.uint8) if by_id else None}
+
+
+def keys_take(keys, idx):
+    """The keys `idx` of a cluster_keys dict."""
+    k = len(keys["conv"])
+    return {f: (None if v is None else v.reshape(k, -1)[idx].reshape(-1)) for f, v in keys.items()}
+
+
+def keys_cat(parts):
+    return {f: (None if parts[0][f] is None else np.concatenate([p[f] for p in parts])) for f in parts[0]}
+
+
+def keys_batch(keys):
+    """One VALID DATA packet per key."""
+    n = len(keys["conv"])
+    return {"status": np.ones(n, np.int8), "cmd": None, "hit": None, "conv": keys["conv"], "dst": keys["dst"], "id": keys["id"],
+            "ctl_kind": None, "ctl_arg": None}
+
+
+def scenario_cluster_index(rc, length, shape, by_dst, by_id, wrap, device, codec=None):
+    """conn_ref.scenario_cluster for the conv table's key forms: every row LIVE, capacity = length, every key probing
+    from one entry (two_homes: from H and H + 1 in turn; duplicates: a third of the rows repeat a key of the run).
+    n_dup, the read-back proof that the index is one run from the predicted entry, rsk_conn.h's contract, and the
+    resolve of every present key (the lowest row wins), of absent keys of the same home, of the neighbouring homes and
+    of the entries at and behind the run's end."""
+    from tests import collide as X
+
+    home = R.CR.WRAP_HOME if wrap else R.CR.INNER_HOME
+    cap, slots = length, X.conn_slots(length)
+    rng = np.random.default_rng(length * 16 + by_dst * 8 + by_id * 4 + wrap * 2 + len(shape))
+    if shape == "two_homes":
+        a, b = cluster_keys((cap + 1) // 2, by_dst, by_id, home, slots), cluster_keys(cap // 2, by_dst, by_id, home + 1, slots, salt=1)
+        order = np.argsort(np.concatenate([np.arange(0, cap, 2), np.arange(1, cap, 2)]), kind="stable")
+        keys = keys_take(keys_cat([a, b]), order)
+    else:
+        keys = cluster_keys(cap, by_dst, by_id, home, slots)
+        if shape == "duplicates":
+            src = np.arange(cap)
+            rep = rng.permutation(cap)[: cap // 3]
+            src[rep] = rng.integers(0, cap, len(rep))
+            keys = keys_take(keys, src)
+    keys = keys_take(keys, rng.permutation(cap))
+    cols = R.random_columns(rng, cap, by_dst, by_id)
+    for f, v in keys.items():
+        if v is not None:
+            cols[f][:] = v
+    cols["state"][:] = LIVE | (rng.integers(0, 2, cap) << 1).astype(np.uint8)
+    tmap, dup = R.table_map(cols, by_dst, by_id)
+    distinct = cap - dup
+    absent = [cluster_keys(8, by_dst, by_id, home, slots, salt=3, base=cap)] + \
+             [cluster_keys(3, by_dst, by_id, home + d, slots, salt=4 + j, base=cap) for j, d in enumerate((-1, 1, 2, cap - 1, cap))]
+    probe = keys_batch(keys_cat([keys] + absent))
+    got, want, tab = R.check_case(rc, cols, probe, by_dst, by_id, device, codec)
+    nd = torch.full((1,), -1, dtype=torch.int32, device=device)
+    tab.rebuild(codec, n_dup=nd)
+    assert int(R.host(nd, np.uint32)[0]) == dup and (dup > 0) == (shape == "duplicates")
+    X.one_run(tab.index.cpu().numpy(), home, distinct)
+    assert R.check_index(tab, cols, by_dst, by_id) == distinct
+    assert bool((got["conv_row"][:cap] != NONE).all()) and bool((got["conv_row"][cap:] == NONE).all())
+    assert got["n_unknown"] == len(probe["status"]) - cap
+    return distinct
+
+
+def scenario_cluster(rc, capacity, by_dst, by_id, wrap, device, codec=None):
+    """A conv table whose keys, and the keys born into it, all probe from one entry.  An eighth of the rows LIVE; a
+    create from 3 x capacity packets fills the table, so the run is as long as the table has rows; the list form
+    closes every second row; a second create fills the table again, in place, in the index AS THE CLOSE LEFT IT;
+    (BY_DST) resets close a third of the rows under HOLD, which the index forgets while they stay LIVE; the list form
+    closes the rest.  After every step the occupied entries are one run from the predicted entry, the index keeps
+    rsk_conn.h's contract, and every lookup, list and column equals the restatements'."""
+    from tests import collide as X
+
+    home = R.CR.WRAP_HOME if wrap else R.CR.INNER_HOME
+    rng = np.random.default_rng(capacity * 8 + by_dst * 4 + by_id * 2 + wrap)
+    cap = capacity
+    rows = np.sort(rng.permutation(cap)[: max(cap // 8, 1)])
+    k1 = cap - len(rows)
+    k2 = len(range(0, cap, 2))
+    keys = cluster_keys(len(rows) + k1 + k2 + 8, by_dst, by_id, home, X.conn_slots(cap))
+    part = lambda lo, hi: keys_take(keys, np.arange(lo, hi))  # noqa: E731
+    cols = R.random_columns(rng, cap, by_dst, by_id)
+    for f, v in part(0, len(rows)).items():
+        if v is not None:
+            cols[f].reshape(cap, -1)[rows] = v.reshape(len(rows), -1)
+    cols["state"][rows] = LIVE | (rng.integers(0, 2, len(rows)) << 1).astype(np.uint8)
+
+    def batch(lo, hi, n, known_from):
+        """n packets: known keys of `known_from`'s LIVE rows and the keys lo..hi, each of those at least once."""
+        new = part(lo, hi)
+        live = np.nonzero(known_from["state"] & LIVE)[0]
+        which = np.concatenate([np.arange(hi - lo), rng.integers(0, hi - lo, n // 2), -1 - rng.integers(0, len(live), n - n // 2 - (hi - lo))])
+        which = rng.permutation(which)
+        r = live[np.maximum(-1 - which, 0)]
+        w = np.maximum(which, 0)
+        pick = lambda f, width=1: np.where((which >= 0)[:, None], new[f].reshape(hi - lo, width)[w],  # noqa: E731
+                                           known_from[f].reshape(cap, width)[r]).reshape(-1)
+        return {"status": np.ones(n, np.int8), "cmd": None, "hit": None, "conv": pick("conv"), "dst": pick("dst") if by_dst else None,
+                "id": pick("id", 8) if by_id else None, "ctl_kind": None, "ctl_arg": None}
+
+    run = lambda tab, m: X.one_run(tab.index.cpu().numpy(), home, m)  # noqa: E731
+    n = 3 * cap
+    # the create fills the table: one run as long as the table has rows
+    got, ref, tab, _b = C.resolve_create(rc, cols, batch(len(rows), len(rows) + k1, n, cols), by_dst, by_id, device, codec)
+    assert got["n_new"] == k1 and got["n_unknown"] == 0
+    run(tab, cap)
+    # the list form closes every second row; no rebuild behind it
+    now = ref["cols"]
+    lst = rng.permutation(np.arange(0, cap, 2)).astype(np.uint32)
+    cref = close_ref(now["state"], close_rows=lst, n_close=len(lst), m_max=len(lst))
+    compare(run_close(rc, tab, device, codec, close_rows=lst, n_close=len(lst)), cref)
+    C.compare_table(tab, dict(now, state=cref["state"]))
+    check_lookups(rc, tab, now, cref["lookup_state"], by_dst, by_id, device, codec)
+    now = dict(now, state=cref["state"])
+    run(tab, cap - k2)
+    # a second create, in place, into the run as the close left it
+    c2 = batch(len(rows) + k1, len(rows) + k1 + k2, n, now)
+    res_want = R.resolve_ref(now, by_dst, by_id, c2)
+    res = R.run_resolve(rc, tab, c2, device, codec, msg_mode="none")
+    R.compare(res, res_want)
+    after = dict(now, cur_in=now["cur_in"] + res_want["add"])
+    ref2 = C.create_ref(after, by_dst, by_id, c2, res["conv_row"], res["unknown"], n)
+    C.compare(C.run_create(rc, tab, C.Batch(c2, res["conv_row"], res["unknown"], device), n, codec), ref2)
+    now = ref2["cols"]
+    C.compare_table(tab, now)
+    C.check_lookups(rc, tab, now, by_dst, by_id, device, codec)
+    assert ref2["n_new"] == k2 and ref2["n_unknown"] == 0
+    run(tab, cap)
+    left = cap
+    if by_dst:  # one CONV_RST (its last word on its key) for every third row, closed under HOLD
+        hit = np.arange(1, cap, 3)
+        idb = None if not by_id else now["id"].reshape(cap, 8)[hit].reshape(-1)
+        c3 = {"status": np.ones(len(hit), np.int8), "cmd": np.full(len(hit), A.CMD_CONV_RST, np.uint8), "hit": None,
+              "conv": rng.integers(0, 2**32, len(hit), dtype=np.uint64).astype(np.uint32), "dst": now["dst"][hit], "id": idb,
+              "ctl_kind": np.full(len(hit), A.CTL_CONV_RST, np.uint8), "ctl_arg": now["conv"][hit].astype(np.uint64)}
+        res = R.run_resolve(rc, tab, c3, device, codec, msg_mode="none")
+        assert np.array_equal(res["conv_row"], hit.astype(np.uint32))
+        href = close_ref(now["state"], True, res["rst_first"], c3["ctl_kind"], res["conv_row"], res["unknown"], res["n_unknown"])
+        compare(run_close(rc, tab, device, codec, hold=True, rst_first=res["rst_first"], ctl_kind=c3["ctl_kind"],
+                          conv_row=res["conv_row"], unknown=res["unknown"], n_unknown=res["n_unknown"]), href)
+        assert href["n_closed"] == len(hit) and np.array_equal(href["state"], now["state"])
+        check_table(rc, tab, now, href, by_dst, by_id, device, codec, hold=True)  # the index forgets rows that stay LIVE
+        left = cap - len(hit)
+        run(tab, left)
+    # then the rest
+    lst = rng.permutation(cap).astype(np.uint32)
+    cref = close_ref(now["state"], close_rows=lst, n_close=cap, m_max=cap)
+    compare(run_close(rc, tab, device, codec, close_rows=lst, n_close=cap), cref)
+    check_table(rc, tab, now, cref, by_dst, by_id, device, codec)
+    assert not (cref["state"] & LIVE).any()
+    run(tab, 0)
+    return k1 + k2

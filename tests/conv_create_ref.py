@@ -148,21 +148,27 @@ def compare_table(tab, want_cols):
 
 
 def check_lookups(rc, tab, cols, by_dst, by_id, device, codec=None):
-    """Every LIVE row's key, looked up through the resolve on the index as it stands, finds the key's lowest row."""
+    """Every LIVE row's key, looked up through the resolve, finds the key's lowest row, and the index keeps
+    rsk_conn.h's contract (the in-place inserts leave what a build leaves): on the index as it stands, and on a
+    rebuilt copy of the table (the table itself goes on with the index as the create left it)."""
     live = np.nonzero(cols["state"] & A.CONN_LIVE)[0]
-    if len(live) == 0:
-        return
     tmap, _ = R.table_map(cols, by_dst, by_id)
     c = {"status": np.ones(len(live), np.int8), "cmd": None, "hit": None, "conv": cols["conv"][live],
          "dst": cols["dst"][live] if by_dst else None, "id": cols["id"].reshape(-1, 8)[live].ravel() if by_id else None,
          "ctl_kind": None, "ctl_arg": None}
     idw = R.id_words(cols["id"] if by_id else None, len(cols["state"]))
     want = np.array([tmap[R.row_key(cols, r, by_dst, by_id, idw)] for r in live.tolist()], np.uint32)
-    saved = None if tab.cur_in is None else tab.cur_in.clone()
-    got = R.run_resolve(rc, tab, c, device, codec, want=("n_unknown",), msg_mode="none")
-    if saved is not None:
-        tab.cur_in.copy_(saved)
-    assert np.array_equal(got["conv_row"], want) and got["n_unknown"] == 0
+    rebuilt = tab.to(device)
+    rebuilt.rebuild(codec)
+    for t, what in ((tab, "index as the create left it"), (rebuilt, "index rebuilt")):
+        R.check_index(t, cols, by_dst, by_id, what=what)
+        if len(live) == 0:
+            continue
+        saved = None if t.cur_in is None else t.cur_in.clone()
+        got = R.run_resolve(rc, t, c, device, codec, want=("n_unknown",), msg_mode="none")
+        if saved is not None:
+            t.cur_in.copy_(saved)
+        assert np.array_equal(got["conv_row"], want) and got["n_unknown"] == 0, what
 
 
 def resolve_create(rc, cols, c, by_dst, by_id, device, codec=None, u_max=None, absent=(), want=OPTIONAL, repeat=False):
@@ -490,3 +496,34 @@ def check_einval(rc, device, codec=None):
             pw *= 2
         mw = (2 * ((u + 63) // 64) + 3) // 4 * 4
         assert L.rsk_conv_create_bytes(u, cap) == (4 * (16 + mw + pw + u + 2 * min(u, cap)) + 15) // 16 * 16, (u, cap)
+
+
+# ---- exact counts of the create on rows that collide in the LDS aggregator -------------------------------------
+def scenario_band_create(rc, n, pattern, device, codec=None, cache=None):
+    """A 2^18-row client table whose only vacant rows are conv_ref.band_rows(): the convs born in the call take
+    them in first-arrival order, so the packets' rows share one run of the count pass's LDS table.  conv_row,
+    the lists and cur_in (a new conv starts at zero) against np.bincount, exactly."""
+    tab, cols, band = R.band_table(rc, device, codec, cache, vacant_band=True)
+    tab.load(**{k: cols[k] for k in TABLE_COLS if cols.get(k) is not None})
+    tab.rebuild(codec)
+    want_row = R.band_packets(band, n, pattern)
+    # the key of a packet is the conv the band's row held (not LIVE: the table does not know it)
+    c = {"conv": cols["conv"][want_row], "dst": None, "id": None}
+    _u, first, inv = np.unique(want_row, return_index=True, return_inverse=True)
+    rank = np.argsort(np.argsort(first))  # distinct key -> its place in first-arrival order
+    row = band[rank[inv]]
+    k = len(first)
+    b = Batch(c, np.full(n, NONE, np.uint32), np.full(n, VALID, np.int8), device)
+    got = run_create(rc, tab, b, n, codec)
+    assert got["tail_ok"] and got["n_unknown"] == 0 and got["n_full"] == 0 and got["n_new"] == k
+    assert np.array_equal(got["conv_row"], row) and bool((got["unknown"] == DROP).all())
+    assert np.array_equal(got["new_rows_all"][:k], band[:k]) and np.array_equal(got["new_first_all"][:k], np.sort(first))
+    state = cols["state"].copy()
+    state[band[:k]] = A.CONN_LIVE
+    cur = cols["cur_in"].copy()
+    cur[band[:k]] = 0
+    cur += np.bincount(row, minlength=len(cur)).astype(np.uint32)
+    assert np.array_equal(tab.column("state"), state)
+    assert np.array_equal(tab.column("cur_in"), cur), np.nonzero(tab.column("cur_in") != cur)[0][:8]
+    assert np.array_equal(tab.column("conv")[band[:k]], c["conv"][np.sort(first)])
+    return k

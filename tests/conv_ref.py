@@ -52,6 +52,24 @@ def table_map(cols, by_dst, by_id):
     return m, dup
 
 
+INVARIANT_MAX = 4097  # the harnesses check the index's structure up to this capacity (the issue's bound; larger tables are sparse)
+
+
+def check_index(tab, cols, by_dst, by_id, live=None, what=""):
+    """tests/collide.index_invariant on the conv table's index as it stands: the key word is conv (| dst << 32),
+    the id word the IdBuf's.  `live`: the rows the index has to hold when they are not the LIVE rows of cols."""
+    from tests import collide as X
+
+    cap = len(cols["state"])
+    if cap > INVARIANT_MAX:
+        return None
+    key = cols["conv"].astype(np.uint64)
+    if by_dst:
+        key |= cols["dst"].astype(np.uint64) << np.uint64(32)
+    return X.index_invariant(tab.index.cpu().numpy(), cap, cols["state"], key, id_words(cols["id"], cap) if by_id else None,
+                             by_id, live=live, what=what)
+
+
 def examined(c):
     ex = np.asarray(c["status"]) == A.RECV_VALID
     if c.get("cmd") is not None:
@@ -740,3 +758,83 @@ def check_einval(rc, device, codec=None):
             assert resolve(*ctx, ref(t), nn, ref(i), ref(o), *tail) == A.OK, label
     if codec is not None:
         torch.cuda.synchronize()
+
+
+# ---- exact counts on rows that collide in the LDS aggregator (tests/collide.py) -----------------------------------
+BAND_CAPACITY = 1 << 18
+BAND_SIZES = (2048, 2049, 4097)  # one 2048-packet tile, one packet into the next, two tiles and one packet
+BAND_PATTERNS = ("distinct", "thrice", "half_one_row")
+PRESET = 0xFFFFFFF0
+
+
+def band_rows():
+    """2560 rows of a 2^18-row table whose homes in tile_count_rows' LDS table lie in one band of 40 entries
+    across its end: more distinct rows than a tile has packets, all probing one wrapping run."""
+    from tests import collide as X
+
+    band = X.rows_in_band(BAND_CAPACITY, X.AGG_SLOTS - 32, 40)
+    assert len(band) == 2560, "tests/collide.py: the aggregator's band has another size"
+    return band
+
+
+def band_packets(band, n, pattern):
+    """The row each of n packets names: per 2048-packet tile 2048 distinct rows of the band; every row three times
+    in random order (the leader rounds take some, the table the rest); or half a tile on one row and the other
+    half on distinct rows."""
+    rng = np.random.default_rng(n + len(pattern))
+    tiles = (n + 2047) // 2048
+    if pattern == "distinct":
+        rows = np.concatenate([np.roll(band, -512 * t)[:2048] for t in range(tiles)])[:n]
+        assert all(len(np.unique(rows[t * 2048: (t + 1) * 2048])) == min(2048, n - t * 2048) for t in range(tiles))
+    elif pattern == "thrice":
+        rows = rng.permutation(np.repeat(band[: (n + 2) // 3], 3))[:n]
+    else:
+        rows = np.concatenate([np.roll(band, -300 * t)[:2048] for t in range(tiles)])[:n]
+        rows[0::2] = band[7]
+    return rows.astype(np.uint32)
+
+
+def band_table(rc, device, codec=None, cache=None, vacant_band=False):
+    """A client table (the conv alone is the key) of 2^18 rows, every row's conv its own; LIVE only on the band's
+    rows, or (vacant_band) on every row but those.  Built once per side: -> (tab, cols, band)."""
+    key = (str(device), vacant_band)
+    if cache is not None and key in cache:
+        return cache[key]
+    band = band_rows()
+    cols = random_columns(np.random.default_rng(5), BAND_CAPACITY, False, False)
+    cols["conv"][:] = np.arange(BAND_CAPACITY, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(9)
+    cols["state"][:] = A.CONN_LIVE if vacant_band else 0
+    cols["state"][band] = 0 if vacant_band else A.CONN_LIVE
+    got = (make_table(rc, cols, device, False, False, codec), cols, band)
+    if cache is not None:
+        cache[key] = got
+    return got
+
+
+def scenario_band_counts(rc, call, n, pattern, device, codec=None, cache=None):
+    """rsk_conv_resolve_batch's cur_in or rsk_conv_send_batch's cur_out over packets whose rows share one run of
+    the aggregator's LDS table, from counters preset just below the 32-bit wrap: np.bincount, exactly."""
+    tab, cols, band = band_table(rc, device, codec, cache)
+    rows = band_packets(band, n, pattern)
+    col = "cur_in" if call == "resolve" else "cur_out"
+    before = np.full(BAND_CAPACITY, PRESET, np.uint32)
+    tab.load(**{col: before})
+    other = {k: tab.column(k) for k in COUNTERS if k != col}
+    if call == "resolve":
+        c = {"status": np.ones(n, np.int8), "cmd": None, "conv": cols["conv"][rows], "id": None, "dst": None, "hit": None,
+             "ctl_kind": None, "ctl_arg": None}
+        got = run_resolve(rc, tab, c, device, codec, want=("n_unknown",), msg_mode="none")
+        assert got["tail_ok"] and got["n_unknown"] == 0 and np.array_equal(got["conv_row"], rows)
+    else:
+        sent = np.full(n, 40, np.int32)
+        sent[n // 2] = 0  # a packet that was not sent does not count
+        got = run_send(rc, tab, rows, device, codec, sent=sent, cols=("ok", "n_bad"))
+        assert got["n_bad"] == 0 and bool((got["ok"] == 1).all())
+        rows = np.delete(rows, n // 2)
+    want = (before.astype(np.uint64) + np.bincount(rows, minlength=BAND_CAPACITY).astype(np.uint64)).astype(np.uint32)
+    cur = tab.column(col)
+    assert np.array_equal(cur, want), (col, np.nonzero(cur != want)[0][:8])
+    assert pattern != "half_one_row" or int(cur.min()) < PRESET  # more than 15 packets on a row: the wrap happened
+    for k, v in other.items():
+        assert np.array_equal(tab.column(k), v), k
+    return int(np.bincount(rows).max())

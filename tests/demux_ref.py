@@ -139,3 +139,29 @@ def check_segments(segs, status, cmd, out, server: bool, id=None):
         _, first = np.unique(seen, return_index=True)
         order = seen[np.sort(first)]
         assert np.array_equal(order, np.arange(len(order))), f"{col}s created in another order"
+
+
+def segments_ref(status, cmd, fields, ids=None, conv=None, ckey=None, dst=None):
+    """rsk_demux_batch without a hash: a dict keyed by the selected fields plus the epoch, filled in arrival
+    order.  The epoch of a packet is the number of VALID control packets (cmd != DATA) before it with CMD_BARRIER,
+    that number among the packets of its own IdBuf with GROUP_BARRIER, and 0 without a barrier; under either
+    barrier a control packet is a segment of its own.  -> (segments, n_valid) as tests/oracle_lib's demux_batch:
+    a list of (first packet, [packets]) in the order of the first packets."""
+    barrier = fields & (A.DEMUX_CMD_BARRIER | A.DEMUX_GROUP_BARRIER)
+    idw = None if ids is None else np.ascontiguousarray(ids, np.uint8).reshape(-1, 8).view(np.uint64).ravel()
+    segs, at, seen = [], {}, {}
+    valid = np.nonzero(np.asarray(status) == A.RECV_VALID)[0].tolist()
+    for i in valid:
+        scope = int(idw[i]) if fields & A.DEMUX_GROUP_BARRIER else None
+        if barrier and cmd[i] != A.CMD_DATA:
+            seen[scope] = seen.get(scope, 0) + 1
+            segs.append((i, [i]))
+            continue
+        key = (seen.get(scope, 0),
+               int(idw[i]) if fields & A.DEMUX_ID else None, int(ckey[i]) if fields & A.DEMUX_CONN_KEY else None,
+               int(conv[i]) if fields & A.DEMUX_CONV else None, int(dst[i]) if fields & A.DEMUX_DST else None)
+        if key not in at:
+            at[key] = len(segs)
+            segs.append((i, []))
+        segs[at[key]][1].append(i)
+    return segs, len(valid)

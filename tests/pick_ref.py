@@ -515,3 +515,62 @@ def check_einval(rc, device, codec=None):
         torch.cuda.synchronize()
     assert int(nn.cpu().numpy().view(np.uint32)[0]) == 0
     assert lib.rsk_conn_pick_bytes(1, 0) % 16 == 0 and lib.rsk_conn_pick_bytes(A.CONN_MAX_ROWS, 1) % 16 == 0
+
+
+def group_taken(tab):
+    """Which entries of the pick index's group table are taken (rsk_pick.h: [4 + 2 C4 + S, + 4 S), 16 B per entry
+    {IdBuf word, offset, count}, count 0 = free), read back from a BY_ID table's pick index."""
+    from tests import collide as X
+
+    cap = tab.capacity
+    c4, slots = (cap + 3) & ~3, X.conn_slots(cap)
+    pick = tab.pick.cpu().numpy().view(np.uint32)
+    assert len(pick) == 4 + 2 * c4 + 5 * slots, "tests/pick_ref.py: rsk_pick.h's layout has changed"
+    return pick[4 + 2 * c4 + slots:].reshape(slots, 4)[:, 3] != 0
+
+
+def check_group_run(tab, cols, home):
+    """The proof that ids built to share a pick home do: on a freshly built pick index the taken group entries are
+    one run from the predicted entry, as many as there are groups with a candidate."""
+    from tests import collide as X
+
+    groups = sum(1 for g in candidates(cols["state"], cols["id"], True).values() if len(g))
+    X.run_of(group_taken(tab), home, groups, "the constructed IdBufs' group entries")
+    return groups
+
+
+# ---- constructed clusters (tests/collide.py) -------------------------------------------------------------------
+def scenario_colliding_groups(rc, groups, device, codec=None, wrap=True):
+    """`groups` IdBufs whose group entries in the pick index all probe from one entry (a run of `groups` entries,
+    across the index's end when `wrap`), one to four candidates each and some rows that are no candidates; the conn
+    keys probe from one entry of the conn index too, so the avoid keys walk its run.  Draws over every group, avoid
+    keys of the group, of another group and of nobody, and ids of the same home that no row has."""
+    from tests import collide as X
+
+    home = CR.WRAP_HOME if wrap else CR.INNER_HOME
+    rng = np.random.default_rng(groups + wrap)
+    cap = 3 * groups
+    gids = X.ids_at(home, groups + 3)
+    assert {X.group_home(int(g), cap) for g in gids} == {home % X.conn_slots(cap)}
+    w = gids[np.concatenate([np.arange(groups), rng.integers(0, groups, cap - groups)])][rng.permutation(cap)]
+    cols = CR.random_columns(rng, cap, by_id=True)
+    CR.place(cols, np.arange(cap), X.keys_at(home, cap, w), id=id_bytes(w))
+    cols["state"][rng.random(cap) < 0.15] = A.CONN_LIVE  # LIVE, not ALIVE: in the conn index, no candidate
+    per = 4
+    wi = np.repeat(np.concatenate([gids, gids[:2]]), per)  # the last ids: no row has them
+    n = len(wi)
+    rows = rng.integers(0, cap, n)
+    own = np.array([rng.choice(np.nonzero(w == i)[0]) if (w == i).any() else 0 for i in wi])
+    kind = np.arange(n) % per
+    avoid = np.where(kind == 0, 0, np.where(kind == 1, cols["conn_key"][own], cols["conn_key"][rows])).astype(np.uint64)
+    avoid[kind == 3] = X.keys_at(home, int((kind == 3).sum()), wi[kind == 3], salt=5)  # absent, walks the whole run
+    draw = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    draw[: EDGE_DRAWS.size] = EDGE_DRAWS
+    tab = make_table(rc, cols, True, device, codec)
+    if codec is not None:
+        torch.cuda.synchronize()
+    CR.check_index(tab, cols, True)
+    assert check_group_run(tab, cols, home) > groups // 2  # some one-row groups lost their only candidate
+    got, want = check(rc, cols, True, n, device, codec, tab=tab, id=id_bytes(wi), avoid_key=avoid, draw=draw)
+    assert want[1] >= 2 * per and int((want[0] != NONE).sum()) > n // 2
+    return n

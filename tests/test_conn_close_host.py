@@ -49,6 +49,14 @@ def test_emptied_group_keeps_probe_chains(capacity):
     K.scenario_probe_chains(rc, capacity, "cpu")
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("by_id", [False, True])
+@pytest.mark.parametrize("capacity", K.COLLIDE_LENGTHS)
+def test_constructed_cluster(capacity, by_id, wrap):
+    """A full table that is one run of the index (and of the pick's group entries), closed in halves and group by group."""
+    assert K.scenario_collide_close(rc, capacity, by_id, wrap, "cpu") == capacity
+
+
 @pytest.mark.parametrize("name", K.WALK_CASES)
 def test_reference_pin_walk(name):
     K.scenario_walk_golden(rc, name, "cpu")

@@ -41,6 +41,19 @@ def test_patterns(capacity, by_id):
     R.scenario_patterns(rc, capacity, by_id, "cpu")
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("by_id", [False, True])
+@pytest.mark.parametrize("capacity,live0,k", R.COLLIDE_CASES)
+def test_constructed_cluster(capacity, live0, k, by_id, wrap):
+    """Table keys, new keys, offered 4-tuples and group ids that all probe from one entry (tests/collide.py)."""
+    assert R.scenario_collide(rc, capacity, live0, k, by_id, wrap, "cpu") > capacity // 2
+
+
+@pytest.mark.parametrize("capacity", [257, 1025])
+def test_constructed_cluster_of_new_groups(capacity):
+    assert R.scenario_collide_groups(rc, capacity, "cpu") == 70
+
+
 @pytest.mark.parametrize("by_id", [False, True])
 def test_groups_grow_and_are_reborn(by_id):
     assert R.scenario_groups(rc, by_id, "cpu") > 100

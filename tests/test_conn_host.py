@@ -93,6 +93,19 @@ def test_host_duplicates_lowest_row_wins():
         assert conn[k] == np.nonzero(live & (keys == k))[0][0]
 
 
+CLUSTERS = ([(n, shape, by_id, True) for n in R.CLUSTER_LENGTHS for by_id in (False, True)
+             for shape in (R.CLUSTER_SHAPES_BY_ID if by_id else R.CLUSTER_SHAPES)] +
+            [(65, "one_home", False, False), (257, "two_homes", True, False), (1025, "duplicates", False, False),
+             (2049, "one_home", False, True), (2049, "one_key_many_ids", True, True)])
+
+
+@pytest.mark.parametrize("length,shape,by_id,wrap", CLUSTERS)
+def test_host_constructed_cluster(length, shape, by_id, wrap):
+    """A table whose keys all probe from one entry (tests/collide.py): a run as long as the table has rows, across
+    the index's end and inside it; n_dup, rsk_conn.h's contract on the index, and every lookup."""
+    assert R.scenario_cluster(rc, length, shape, by_id, wrap, "cpu") > length // 2
+
+
 def test_host_state_changes_with_rebuild():
     rng = np.random.default_rng(4)
     cols = R.random_columns(rng, 16)

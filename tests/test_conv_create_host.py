@@ -53,6 +53,16 @@ def test_skew(kind):
     C.scenario_skew(rc, kind, "cpu")
 
 
+BAND_TABLES = {}
+
+
+@pytest.mark.parametrize("pattern", R.BAND_PATTERNS)
+@pytest.mark.parametrize("n", R.BAND_SIZES)
+def test_counts_on_colliding_rows(n, pattern):
+    """The convs born in the call take rows that share one run of the device's LDS row table (tests/collide.py)."""
+    assert C.scenario_band_create(rc, n, pattern, "cpu", cache=BAND_TABLES) > 600
+
+
 def test_reads():
     C.scenario_reads(rc, "cpu")
 

@@ -41,6 +41,18 @@ def test_host_skew(kind):
     R.scenario_skew(rc, kind, "cpu")
 
 
+BAND_TABLES = {}
+
+
+@pytest.mark.parametrize("pattern", R.BAND_PATTERNS)
+@pytest.mark.parametrize("n", R.BAND_SIZES)
+@pytest.mark.parametrize("call", ["resolve", "send"])
+def test_host_counts_on_colliding_rows(call, n, pattern):
+    """The counts over rows that share one run of the device's LDS row table (tests/collide.py): the twin's
+    sums are the same np.bincount."""
+    R.scenario_band_counts(rc, call, n, pattern, "cpu", cache=BAND_TABLES)
+
+
 def test_host_conv_rst():
     R.scenario_conv_rst(rc, "cpu")
 

@@ -91,6 +91,21 @@ def test_reference_pin(cx, gpu, name):
     assert n_miss == R.GOLDEN_CLIENT[name][1]
 
 
+# ---- 1b. constructed clusters ------------------------------------------------------------------------
+def _clusters():
+    from tests.test_conn_host import CLUSTERS
+
+    return CLUSTERS
+
+
+@pytest.mark.parametrize("length,shape,by_id,wrap", _clusters())
+def test_constructed_cluster(cx, gpu, length, shape, by_id, wrap):
+    """tests/test_conn_host.py's clusters on the device: up to 2049 lanes of one launch insert into one run of the
+    index with compare-and-swap, across its end; n_dup, rsk_conn.h's contract on the index as the build left it
+    (the occupied entries are a sequential insert's, so also the host twin's), and every lookup."""
+    assert R.scenario_cluster(rc, length, shape, by_id, wrap, gpu, cx) > length // 2
+
+
 # ---- 2. the server shape; the missing pairs through the demux ----------------------------------------
 def test_server_shape_missing_pairs_by_demux(cx, gpu):
     import torch

@@ -57,6 +57,15 @@ def test_emptied_group_keeps_probe_chains(cx, gpu, capacity):
     K.scenario_probe_chains(rc, capacity, gpu, cx)
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("by_id", [False, True])
+@pytest.mark.parametrize("capacity", K.COLLIDE_LENGTHS)
+def test_constructed_cluster(cx, gpu, capacity, by_id, wrap):
+    """A full table that is one run of the index (and of the pick's group entries, tests/collide.py): every second row
+    closed without and with REMOVE, then the rest; groups of one pick home emptied one by one."""
+    assert K.scenario_collide_close(rc, capacity, by_id, wrap, gpu, cx) == capacity
+
+
 @pytest.mark.parametrize("name", K.WALK_CASES)
 def test_reference_pin_walk(cx, gpu, name):
     K.scenario_walk_golden(rc, name, gpu, cx)

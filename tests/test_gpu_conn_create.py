@@ -53,6 +53,22 @@ def test_patterns(cx, gpu, capacity, by_id):
     R.scenario_patterns(rc, capacity, by_id, gpu, cx)
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("by_id", [False, True])
+@pytest.mark.parametrize("capacity,live0,k", R.COLLIDE_CASES)
+def test_constructed_cluster(cx, gpu, capacity, live0, k, by_id, wrap):
+    """Hundreds of lanes of one launch insert into ONE run of the index, of the dedup table, of the offers table and
+    of the pick's group entries (keys, 4-tuples and ids built to probe from one entry, tests/collide.py), across the
+    tables' ends; the index keeps rsk_conn.h's contract after every call."""
+    assert R.scenario_collide(rc, capacity, live0, k, by_id, wrap, gpu, cx) > capacity // 2
+
+
+@pytest.mark.parametrize("capacity", [257, 1025])
+def test_constructed_cluster_of_new_groups(cx, gpu, capacity):
+    """70 new groups of one pick home born in one call: the claim of taken-off and emptied group entries."""
+    assert R.scenario_collide_groups(rc, capacity, gpu, cx) == 70
+
+
 @pytest.mark.parametrize("by_id", [False, True])
 def test_groups_grow_and_are_reborn(cx, gpu, by_id):
     assert R.scenario_groups(rc, by_id, gpu, cx) > 100

@@ -68,6 +68,19 @@ def test_skew(cx, gpu, kind):
     R.scenario_skew(rc, kind, gpu, cx)
 
 
+BAND_TABLES = {}
+
+
+@pytest.mark.parametrize("pattern", R.BAND_PATTERNS)
+@pytest.mark.parametrize("n", R.BAND_SIZES)
+@pytest.mark.parametrize("call", ["resolve", "send"])
+def test_counts_on_colliding_rows(cx, gpu, call, n, pattern):
+    """tile_count_rows "exact under any skew", on the skew of many rows: 2048 distinct rows of one tile whose
+    entries in the LDS table all start inside one band of 40 across the table's end (one run of 2048 entries),
+    every row three times, and half a tile on one row; cur_in / cur_out from just below the 32-bit wrap."""
+    R.scenario_band_counts(rc, call, n, pattern, gpu, cx, cache=BAND_TABLES)
+
+
 def test_conv_rst(cx, gpu):
     R.scenario_conv_rst(rc, gpu, cx)
 

@@ -35,6 +35,22 @@ def test_reference_pin_flush_close(cx, gpu, name):
     assert K.scenario_flush_golden(rc, name, gpu, cx)["closed"] > 0
 
 
+@pytest.mark.parametrize("length,shape,flags,wrap", K.INDEX_CLUSTERS)
+def test_constructed_cluster_index(cx, gpu, length, shape, flags, wrap):
+    """The conn index's cluster families for the conv table's key forms (tests/collide.py; the client's conv-only keys
+    by search): a full table that is one run of the index, two interleaved homes, duplicates inside the run (the
+    lowest row wins, n_dup), absent keys of the same and of the neighbouring homes."""
+    assert K.scenario_cluster_index(rc, length, shape, flags[0], flags[1], wrap, gpu, cx) > length // 2
+
+
+@pytest.mark.parametrize("capacity,flags,wrap", K.LIFE_CLUSTERS)
+def test_constructed_cluster(cx, gpu, capacity, flags, wrap):
+    """A create that fills the table (a run as long as the table has rows), the list-form close of every second row,
+    a create in place into the index as the close left it, a close under HOLD (BY_DST), then the rest: on a conv table
+    whose keys all probe from one entry of the index, across the index's end or not."""
+    assert K.scenario_cluster(rc, capacity, flags[0], flags[1], wrap, gpu, cx) > capacity // 2
+
+
 @pytest.mark.parametrize("by_dst,by_id", R.FLAG_COMBOS)
 @pytest.mark.parametrize("capacity", K.CAPACITIES)
 def test_timer_random(cx, gpu, capacity, by_dst, by_id):

@@ -70,6 +70,17 @@ def test_skew(cx, gpu, kind):
     C.scenario_skew(rc, kind, gpu, cx)
 
 
+BAND_TABLES = {}
+
+
+@pytest.mark.parametrize("pattern", R.BAND_PATTERNS)
+@pytest.mark.parametrize("n", R.BAND_SIZES)
+def test_counts_on_colliding_rows(cx, gpu, n, pattern):
+    """The count pass of the create on 2048 distinct rows of one tile that share one run of its LDS table, on
+    every row three times and on half a tile on one row: cur_in of the new convs is np.bincount."""
+    assert C.scenario_band_create(rc, n, pattern, gpu, cx, cache=BAND_TABLES) > 600
+
+
 def test_reads(cx, gpu):
     C.scenario_reads(rc, gpu, cx)
 

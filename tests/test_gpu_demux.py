@@ -1,7 +1,9 @@
 """GPU: rsk_demux_batch against the oracle (orc_demux_batch), segment for segment:
 random batches over every field selection, control-packet barriers, all-invalid / all-control /
-single-key / all-distinct batches (1, 2 and 3 radix passes), ragged sizes, and the decoded output
-of the real receive path (C4 frames through rsk_decode_batch, demuxed on the device)."""
+single-key / all-distinct batches (1, 2 and 3 radix passes), ragged sizes, the decoded output
+of the real receive path (C4 frames through rsk_decode_batch, demuxed on the device), and keys
+constructed to collide (tests/collide.py: one hash, one fingerprint, one home, runs across the table's
+end), held to the hash-free tests/demux_ref.segments_ref as well."""
 from __future__ import annotations
 
 import numpy as np
@@ -255,3 +257,148 @@ def test_demux_table_reuse(codec, gpu, oracle):
         got = run_gpu(codec, gpu, *case[:2], fields, *case[2:])
         exp = oracle.demux_batch(case[0], case[1], fields, *case[2:])
         assert got[1] == exp[1] and got[0] == exp[0], (k, n, fields)
+
+
+# ---- constructed collisions (tests/collide.py) ------------------------------------------------------------------
+# Keys built by running key_hash backwards: identical 64-bit hashes, one fingerprint over chosen homes, one home
+# under many fingerprints, runs that cross the table's end.  Every case is compared with tests/demux_ref's
+# segments_ref (a dict, no hash) and with the oracle (which hashes with the same constants), segment for segment.
+def collide_check(codec, gpu, oracle, status, cmd, fields, ids, conv, ckey, dst):
+    from tests import demux_ref as D
+
+    got = run_gpu(codec, gpu, status, cmd, fields, ids, conv, ckey, dst)
+    assert codec.check_device_errors() == 0
+    ref = D.segments_ref(status, cmd, fields, ids, conv, ckey, dst)
+    exp = oracle.demux_batch(status, cmd, fields, ids, conv, ckey, dst)
+    assert got[1] == ref[1] == exp[1] and len(got[0]) == len(ref[0]) == len(exp[0])
+    assert got[0] == ref[0], "against the hash-free reference"
+    assert got[0] == exp[0], "against the oracle"
+    return got[0]
+
+
+def interleaved(rng, k, lo=1, hi=5):
+    """Key numbers 0..k-1, each lo..hi times, shuffled: one key's packets fall into several 512-packet tiles."""
+    p = np.repeat(np.arange(k), rng.integers(lo, hi + 1, k))
+    rng.shuffle(p)
+    return p
+
+
+def batch_of(rng, n, p_valid=0.97):
+    status = np.where(rng.random(n) < p_valid, A.RECV_VALID, A.RECV_DROP).astype(np.int8)
+    return status, np.zeros(n, np.uint8), np.zeros(8 * n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint64), \
+        np.zeros(n, np.uint32)
+
+
+@pytest.mark.parametrize("k", [2, 65, 511, 512, 513, 600])
+@pytest.mark.parametrize("fields", [A.DEMUX_ID | A.DEMUX_CONN_KEY, A.DEMUX_ID | A.DEMUX_CONN_KEY | A.DEMUX_CMD_BARRIER, ALL])
+def test_demux_same_hash(codec, gpu, oracle, k, fields):
+    """k distinct (IdBuf, connKey) keys with ONE 64-bit hash: every key after the first meets the others' entries
+    under its own fingerprint, in the LDS table of its tile and in the global table, and has to be told apart by
+    the full key.  k around the 512 packets of an insert tile."""
+    from tests import collide as X
+
+    rng = np.random.default_rng(k * 8 + fields)
+    idw, ck = X.same_hash(k, salt=fields)
+    which = interleaved(rng, k)
+    n = len(which)
+    status, cmd, _ids, conv, _ck, dst = batch_of(rng, n)
+    conv[:], dst[:] = 7, 0x0A000001
+    if fields & A.DEMUX_CMD_BARRIER:
+        cmd[19::20] = 1 + np.arange(len(cmd[19::20])) % 4
+    segs = collide_check(codec, gpu, oracle, status, cmd, fields, idw[which].view(np.uint8), conv, ck[which], dst)
+    if not fields & A.DEMUX_CMD_BARRIER:
+        assert len(segs) == len(np.unique(which[status == A.RECV_VALID]))
+
+
+@pytest.mark.parametrize("kind", ["same_fp", "same_fp_one_home_each_twice", "same_home"])
+@pytest.mark.parametrize("k", [65, 600])
+def test_demux_fingerprints_and_homes_across_the_wrap(codec, gpu, oracle, kind, k):
+    """One fingerprint over consecutive homes from T - 2 (each entry confirmed and refused on the full key), and
+    one home T - 2 under k fingerprints (a run of k entries across the table's end)."""
+    from tests import collide as X
+
+    rng = np.random.default_rng(k + len(kind))
+    which = interleaved(rng, k)
+    n = len(which)
+    mask = X.dm_table_slots(n) - 1
+    if kind == "same_home":
+        ck = X.same_home(k, mask - 1, mask)
+    else:
+        step = 2 if kind.endswith("twice") else 1
+        ck = X.same_fp(k, [(mask - 1 + j // step) & mask for j in range(k)], mask)
+    status, cmd, ids, conv, _ck, dst = batch_of(rng, n)
+    for fields in (A.DEMUX_CONN_KEY, A.DEMUX_CONN_KEY | A.DEMUX_CMD_BARRIER):  # no control packet: epoch 0 throughout
+        collide_check(codec, gpu, oracle, status, cmd, fields, ids, conv, ck[which], dst)
+
+
+@pytest.mark.parametrize("epochs,per", [(9, 450), (40, 100), (3, 1400)])
+def test_demux_same_hash_in_other_epochs(codec, gpu, oracle, epochs, per):
+    """CONN_KEY | CMD_BARRIER: the packets of epoch e carry the conn keys whose hashes IN THAT EPOCH are two fixed
+    values of one fingerprint and one home (T - 2).  Every epoch's key meets the earlier epochs' owners under its
+    own fingerprint; they lie outside the epoch's packet range, and the probe has to walk past them."""
+    from tests import collide as X
+
+    n = epochs * per
+    rng = np.random.default_rng(n + epochs)
+    mask = X.dm_table_slots(n) - 1
+    hv = [(0xFEEDFACE << 32) | (q * (mask + 1)) | (mask - 1) for q in (1, 2)]
+    status, cmd, ids, conv, ck, dst = batch_of(rng, n)
+    cmd[per - 1::per] = 3
+    cmd[-1] = 0
+    ep = np.concatenate([[0], np.cumsum((cmd != 0) & (status == A.RECV_VALID))[:-1]])
+    keys = np.stack([X.epoch_keys(h, range(int(ep.max()) + 1)) for h in hv])
+    ck[:] = keys[rng.integers(0, 2, n), ep]
+    assert {X.key_hash(ep=int(e), ck=int(c)) for e, c in zip(ep, ck)} == set(hv)
+    segs = collide_check(codec, gpu, oracle, status, cmd, A.DEMUX_CONN_KEY | A.DEMUX_CMD_BARRIER, ids, conv, ck, dst)
+    assert int(ep.max()) >= epochs // 2 and len(segs) >= 2 * (int(ep.max()) + 1)
+
+
+@pytest.mark.parametrize("groups", [2, 65, 300])
+@pytest.mark.parametrize("fields", [A.DEMUX_ID | A.DEMUX_GROUP_BARRIER, ALL | A.DEMUX_GROUP_BARRIER])
+def test_demux_group_barrier_colliding_idbufs(codec, gpu, oracle, groups, fields):
+    """IdBufs whose IdBuf-only keys (the first pass) share fingerprint, table home and LDS home, each with its own
+    control packets, a few with none: every DATA packet takes the count of ITS IdBuf's control packets."""
+    from tests import collide as X
+
+    n = 3000
+    rng = np.random.default_rng(groups + fields)
+    mask = X.dm_table_slots(n) - 1
+    idw = X.ids_same_fp_home(groups, mask)
+    g = rng.integers(0, groups, n)
+    status, cmd, _ids, conv, ck, dst = batch_of(rng, n)
+    quiet = g >= groups - max(groups // 8, 1) if groups > 2 else np.zeros(n, bool)  # IdBufs without a control packet
+    ctrl = (rng.random(n) < 0.12) & ~quiet
+    cmd[ctrl] = rng.integers(1, 5, int(ctrl.sum()))
+    conv[:], ck[:], dst[:] = rng.integers(0, 3, n), rng.integers(0, 2, n) + 0x10002711, 0x0A000001
+    collide_check(codec, gpu, oracle, status, cmd, fields, idw[g].view(np.uint8), conv, ck, dst)
+
+
+def test_demux_colliding_keys_reuse_the_table(codec, gpu, oracle):
+    """test_demux_table_reuse with constructed keys: a batch of few segments (the call clears the entries it
+    claimed), other colliding keys in a table of the same size, a smaller batch, and the first size again."""
+    from tests import collide as X
+
+    def same_hash_call(k, hi, salt, fields):
+        rng = np.random.default_rng(salt)
+        idw, ck = X.same_hash(k, salt=salt)
+        which = interleaved(rng, k, hi - 4, hi)
+        status, cmd, _ids, conv, _ck, dst = batch_of(rng, len(which))
+        if fields & A.DEMUX_CMD_BARRIER:
+            cmd[29::30] = 2
+        collide_check(codec, gpu, oracle, status, cmd, fields, idw[which].view(np.uint8), conv, ck[which], dst)
+        return len(which)
+
+    def same_home_call(k, hi, salt):
+        rng = np.random.default_rng(salt)
+        which = interleaved(rng, k, hi - 4, hi)
+        n = len(which)
+        mask = X.dm_table_slots(n) - 1
+        ck = X.same_home(k, mask - 1, mask)
+        status, cmd, ids, conv, _ck, dst = batch_of(rng, n)
+        collide_check(codec, gpu, oracle, status, cmd, A.DEMUX_CONN_KEY, ids, conv, ck[which], dst)
+        return n
+
+    both = A.DEMUX_ID | A.DEMUX_CONN_KEY
+    sizes = [same_hash_call(65, 50, 1, both), same_home_call(100, 32, 2), same_hash_call(65, 50, 3, both | A.DEMUX_CMD_BARRIER),
+             same_home_call(20, 8, 4), same_hash_call(40, 80, 5, both)]
+    assert len({X.dm_table_slots(s) for s in sizes[:3]}) == 1 and X.dm_table_slots(sizes[3]) < X.dm_table_slots(sizes[0])

@@ -50,6 +50,15 @@ def test_big_group(cx, gpu, m):
     R.scenario_big_group(rc, m, gpu, cx)
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("groups", [65, 1025])
+def test_colliding_groups(cx, gpu, groups, wrap):
+    """65 and 1025 groups whose entries in the pick index all probe from one entry (ids built by running the hash
+    backwards, tests/collide.py): the build's lanes claim one run of entries, across the index's end, and every
+    pick walks it; the avoid keys walk a run of the conn index as long as the table has rows."""
+    assert R.scenario_colliding_groups(rc, groups, gpu, cx, wrap=wrap) > 4 * groups
+
+
 @pytest.mark.parametrize("by_id", [False, True])
 def test_avoid_keys(cx, gpu, by_id):
     R.scenario_avoid(rc, by_id, gpu, cx)

@@ -96,6 +96,13 @@ def test_host_big_group(m):
     R.scenario_big_group(rc, m, "cpu")
 
 
+@pytest.mark.parametrize("wrap", [True, False])
+@pytest.mark.parametrize("groups", [65, 1025])
+def test_host_colliding_groups(groups, wrap):
+    """Groups whose entries in the pick index all probe from one entry (tests/collide.py)."""
+    assert R.scenario_colliding_groups(rc, groups, "cpu", wrap=wrap) > 4 * groups
+
+
 @pytest.mark.parametrize("by_id", [False, True])
 def test_host_avoid_keys(by_id):
     R.scenario_avoid(rc, by_id, "cpu")
