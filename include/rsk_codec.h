@@ -1228,6 +1228,171 @@ int rsk_conn_create_batch(rsk_ctx *ctx, const rsk_conn_table *tab, const rsk_con
 int rsk_conn_create_host(const rsk_conn_table *tab, const rsk_conn_create_rows *rows, uint32_t n,
                          const rsk_conn_create_in *in, const rsk_conn_create_out *out, int nthreads);
 
+/* ---- tuple pool: TcpAckPool and the accepted-socket pool kept on the device ------------------------- */
+/* What feeds rsk_conn_create_batch's offers on a server: TcpAckPool::mInfoPool (net/TcpAckPool.cpp), the handshakes
+ * RawInput harvested, and ServerNetManager::mPool (server/ServerNetManager.cpp), the accepted sockets nobody has
+ * asked for yet; both std::maps keyed by the 4-tuple (TcpCmpFn: src, sp, dst, dp).  One type serves both: caller-
+ * owned device columns of `capacity` rows (capacity in [1, RSK_CONN_MAX_ROWS]) and an index of
+ * rsk_conn_index_bytes(capacity, RSK_CONN_BY_ID) bytes, 16-B aligned, with the layout, hash and probe rule of the
+ * conn index, keyed by (src << 32 | dst, sp << 16 | dp) as the create's offers are hashed: an index built on either
+ * side is valid on the other.  A row is in the pool iff state has RSK_POOL_LIVE.  The ack pool holds its tuples in
+ * the orientation of a DATA packet's TcpInfo (the parse with RSK_PARSE_IS_SERVER reverses a SYN's, RawTcp.cpp:
+ * 221-227) with the stored seq / ack; the socket pool has no use for seq / ack (both may be NULL there).  expiry is
+ * the reference's `now + PersistMs` of the entry, in the caller's clock.
+ *   receive  parse -> rsk_pool_add_batch (ack pool, TOUCH) ; accepted sockets -> rsk_pool_add_batch (socket pool)
+ *            rsk_pool_offers -> resolve -> rsk_conn_create_batch -> rsk_tcp_recv_ack_batch -> rsk_pool_settle_batch
+ *   timer    rsk_pool_flush on either pool
+ * The host reads counts and row lists behind the batch (to bind sockets to the new conns and to close sockets);
+ * the socket objects themselves stay the host's, one per socket-pool row.  Every call is a linear chain of kernels
+ * on `stream` without host state or memset nodes; per-tile counts live in the control path's per-stream scratch
+ * (rsk_reserve_stream before a capture); every call captures into a hipGraph and replays on edited columns.  No
+ * block waits on another, nothing spins, every probe loop is bounded by its table's size, every value read from an
+ * index or a list is bounded before use, a row's state byte is written by the one lane that owns the row, no pass
+ * walks n or a capacity on one block.  Counts are written, not accumulated; nothing behind a list's end is written.
+ *
+ * rsk_pool_index_build / _host: the index over the LIVE rows, after host edits (as rsk_conn_index_build; *n_dup
+ * optional: LIVE rows whose tuple a lower LIVE row holds).  RSK_EINVAL: a NULL ctx or pool, a NULL state, tuple
+ * column, expiry or index, an index not 16-B or an expiry not 8-B aligned, a capacity out of range.
+ *
+ * rsk_pool_add_batch: TcpAckPool::AddInfoFromPeer (net/TcpAckPool.cpp:17-33) for the parse's SYN rows, and
+ * ServerNetManager::add2Pool (server/ServerNetManager.cpp:105-117) for a list of accepted tuples.
+ *   1. Considered: with parse_status given the rows with parse_status[i] == RSK_PARSE_SYN (the columns are the
+ *      parse's rsk_tcpinfo_out as they lie on the device), without it every row (the list form).
+ *   2. A considered row with sp == 0 or dp == 0 is dropped and counted in *n_zero_port (the pool refuses it,
+ *      although the parse reports it).
+ *   3. Of the first u_max remaining rows: a tuple that is LIVE in the pool keeps its row and its seq / ack -- the
+ *      first handshake wins; with RSK_POOL_TOUCH (the ack pool: every AddInfoFromPeer moves the expiry) its expiry
+ *      becomes in->expiry, without it (the socket pool, whose emplace changes nothing) it stays.
+ *   4. The distinct tuples that are not LIVE take the vacant rows, lowest first, in first-arrival order, each with
+ *      the columns of its first arrival (seq / ack where the pool has them), expiry = in->expiry, state = LIVE.
+ *      n_new = min(distinct, vacant); *n_full = the rest (DEVIATION: the reference's map is unbounded);
+ *      *n_again = the rows of step 3 whose tuple was LIVE already or arrived earlier in the call.
+ *   5. The new rows go into the index by compare-and-swap in a later launch than the one that writes the rows; the
+ *      index is never rebuilt, and a call that adds nothing writes no byte of it.
+ *   6. row[i] (optional, [n]) = the row the tuple of input i has after the call for a row that passed step 2
+ *      (whether or not it was among the first u_max), RSK_CONN_NONE for every other and for a tuple without a row;
+ *      new_rows[j] / new_first[j] (optional, [min(u_max, capacity)]) = the j-th new row and its first arrival.
+ * work: rsk_pool_add_bytes(u_max, capacity) bytes, 16-B aligned, caller-owned, contents do not matter, one per
+ * stream that runs the call.  RSK_EINVAL: a NULL ctx, in, out or work; a pool as for rsk_pool_index_build; flags
+ * other than RSK_POOL_TOUCH; u_max 0 or above 2^24; n > 0 with a NULL tuple column, or a NULL seq / ack where the
+ * pool has that column; new_rows or new_first without n_new; work not 16-B aligned; n > RSK_MAX_BATCH.
+ *
+ * rsk_pool_offers: the join GetTcp (server/ServerNetManager.cpp:52-75) and Wait2TransferInfo (net/TcpAckPool.cpp:
+ * 35-60) make per miss, ahead of time.  Every LIVE row of the ack pool whose tuple is LIVE in the socket pool makes
+ * one offer, in ascending ack-pool row order, into columns laid out as rsk_conn_offers (m_max entries): src, dst,
+ * sp, dp of the record; ack = the record's ack, never its seq; flag = RSK_TH_ACK, never the handshake's; conn_key
+ * (optional) = rsk_key_for_tcp(sp, dp), for a client, which harvests without RSK_PARSE_IS_SERVER, adds its dialled
+ * tuples to the socket pool and hands the offers to the create's list form.  offer_ack_row[o] / offer_sock_row[o]
+ * (optional, [m_max]) = the two rows of offer o; *n_offer = min(matches, m_max); *n_over (optional) = the matches
+ * beyond m_max, which are not offered.  expiry is not consulted: neither GetTcp nor Wait2TransferInfo looks at it,
+ * an entry lives until a flush removes it.  RSK_EINVAL: a NULL ctx, pool or out; pools as above, the ack pool also
+ * without seq or ack; m_max 0 or above 2^21; a NULL src, dst, sp, dp, ack, flag or n_offer; conn_key not 8-B aligned.
+ *
+ * rsk_pool_settle_batch: what becomes of the pools behind the batch.
+ *   (a) For j < min(*n_new, new_max): both rows of offer new_offer[j] (the create's output; offer_ack_row /
+ *       offer_sock_row are rsk_pool_offers', m_max entries) leave their pools; taken_sock_rows[j] (optional,
+ *       [new_max]) = the socket row, whose socket the host binds to the create's new_rows[j].
+ *   (b) Then every packet with miss[i] == RSK_RECV_VALID (the create's miss: a packet CreateNetConn refused) is
+ *       taken by its tuple as the pools stand after (a).  LIVE in both pools: nothing happens, a whole offer this
+ *       call did not consume stays (a full table, or the create's documented deviation).  Otherwise whichever entry
+ *       exists is removed (GetTcp erases the socket it finds, Wait2TransferInfo the record).  Removed socket rows
+ *       are listed once each in row order in closed_sock_rows ([capacity of the socket pool], optional) /
+ *       *n_closed, for the host to close; *n_purged_ack = the ack-pool rows (b) removed.
+ *   The outcome does not depend on packet order: (b) decides from state and the marks of (a) alone, equal lanes
+ *   write equal marks, and LIVE is cleared by the lane that owns the row in a later launch.  Afterwards every
+ *   lookup gives what a rebuild over the new state gives: each pool that lost a row is rebuilt over the rows that
+ *   stay; a pool that lost none has no byte of its index written.
+ * work: rsk_pool_settle_bytes(capacity of the ack pool, of the socket pool) bytes, 16-B aligned, contents do not
+ * matter.  RSK_EINVAL: a NULL ctx, pool, in, out or work; pools as above; m_max 0 or above 2^21, new_max above 2^21;
+ * new_max > 0 with a NULL new_offer, n_new, offer_ack_row or offer_sock_row; n > 0 with a NULL miss or tuple column;
+ * closed_sock_rows without n_closed; work not 16-B aligned; n > RSK_MAX_BATCH.
+ *
+ * rsk_pool_flush: TcpAckPool::OnFlush (net/TcpAckPool.cpp:85-95) and ServerNetManager::OnFlush
+ * (server/ServerNetManager.cpp:82-103), both of which compare expiry <= now: the LIVE rows with expiry <= now_ms
+ * leave the pool; dead_rows ([capacity], optional) lists them in row order, *n_dead counts them (the host closes
+ * the sockets of a socket pool's); the index is rebuilt over the rows that stay only when a row left.  RSK_EINVAL:
+ * a NULL ctx, pool or out; a pool as above; dead_rows without n_dead.
+ *
+ * The host twins take host pointers and the same rules, outputs, work sizes and index layouts; sequential. */
+#define RSK_POOL_LIVE  0x1u  /* state bit: the row holds an entry of the pool                                  */
+#define RSK_POOL_TOUCH 0x1u  /* add flag: a considered row of a LIVE tuple moves its expiry (the ack pool)     */
+typedef struct rsk_pool {    /* device pointers, caller-owned, `capacity` rows */
+    uint8_t  *state;         /* [C] RSK_POOL_LIVE */
+    uint32_t *src, *dst;     /* [C] */
+    uint16_t *sp, *dp;       /* [C] */
+    uint32_t *seq, *ack;     /* [C] the record's; NULL in a socket pool */
+    uint64_t *expiry;        /* [C] */
+    uint32_t *index;         /* rsk_conn_index_bytes(capacity, RSK_CONN_BY_ID) bytes, 16-B aligned */
+    uint32_t capacity;
+} rsk_pool;
+int rsk_pool_index_build(rsk_ctx *ctx, const rsk_pool *pool, uint32_t *n_dup, void *stream);
+int rsk_pool_index_build_host(const rsk_pool *pool, uint32_t *n_dup, int nthreads);
+
+uint64_t rsk_pool_add_bytes(uint32_t u_max, uint32_t capacity);  /* 0 for a bad u_max / capacity */
+typedef struct rsk_pool_add_in {
+    const uint32_t *src, *dst;   /* [n] */
+    const uint16_t *sp, *dp;     /* [n] */
+    const uint32_t *seq, *ack;   /* [n] where the pool has the column */
+    const int8_t *parse_status;  /* [n] optional */
+    uint64_t expiry;             /* now + PersistMs */
+    uint32_t u_max;
+    uint32_t flags;              /* RSK_POOL_TOUCH */
+    void *work;
+} rsk_pool_add_in;
+typedef struct rsk_pool_add_out {  /* every field optional */
+    uint32_t *row;                        /* [n] */
+    uint32_t *new_rows, *new_first;       /* [min(u_max, capacity)] */
+    uint32_t *n_new, *n_again, *n_full, *n_zero_port;  /* [1] */
+} rsk_pool_add_out;
+int rsk_pool_add_batch(rsk_ctx *ctx, const rsk_pool *pool, uint32_t n, const rsk_pool_add_in *in,
+                       const rsk_pool_add_out *out, void *stream);
+int rsk_pool_add_host(const rsk_pool *pool, uint32_t n, const rsk_pool_add_in *in, const rsk_pool_add_out *out,
+                      int nthreads);
+
+typedef struct rsk_pool_offers_out {
+    uint32_t *src, *dst;         /* [m_max] */
+    uint16_t *sp, *dp;           /* [m_max] */
+    uint32_t *ack;               /* [m_max] */
+    uint8_t  *flag;              /* [m_max] */
+    uint64_t *conn_key;          /* [m_max] optional */
+    uint32_t *n_offer;           /* [1] */
+    uint32_t *offer_ack_row, *offer_sock_row;  /* [m_max] optional */
+    uint32_t *n_over;            /* [1] optional */
+    uint32_t m_max;
+} rsk_pool_offers_out;
+int rsk_pool_offers(rsk_ctx *ctx, const rsk_pool *ack_pool, const rsk_pool *sock_pool, const rsk_pool_offers_out *out,
+                    void *stream);
+int rsk_pool_offers_host(const rsk_pool *ack_pool, const rsk_pool *sock_pool, const rsk_pool_offers_out *out,
+                         int nthreads);
+
+uint64_t rsk_pool_settle_bytes(uint32_t cap_ack, uint32_t cap_sock);  /* 0 for a bad capacity */
+typedef struct rsk_pool_settle_in {
+    const uint32_t *new_offer;   /* [new_max] the create's */
+    const uint32_t *n_new;       /* [1] the create's */
+    const uint32_t *offer_ack_row, *offer_sock_row;  /* [m_max] rsk_pool_offers' */
+    uint32_t new_max, m_max;
+    const int8_t *miss;          /* [n] the create's */
+    const uint32_t *src, *dst;   /* [n] the parse's TcpInfo */
+    const uint16_t *sp, *dp;     /* [n] */
+    void *work;
+} rsk_pool_settle_in;
+typedef struct rsk_pool_settle_out {  /* every field optional */
+    uint32_t *taken_sock_rows;   /* [new_max] */
+    uint32_t *closed_sock_rows;  /* [capacity of the socket pool] */
+    uint32_t *n_closed, *n_purged_ack;  /* [1] */
+} rsk_pool_settle_out;
+int rsk_pool_settle_batch(rsk_ctx *ctx, const rsk_pool *ack_pool, const rsk_pool *sock_pool, uint32_t n,
+                          const rsk_pool_settle_in *in, const rsk_pool_settle_out *out, void *stream);
+int rsk_pool_settle_host(const rsk_pool *ack_pool, const rsk_pool *sock_pool, uint32_t n, const rsk_pool_settle_in *in,
+                         const rsk_pool_settle_out *out, int nthreads);
+
+typedef struct rsk_pool_flush_out {
+    uint32_t *dead_rows;         /* [capacity] optional */
+    uint32_t *n_dead;            /* [1] optional */
+} rsk_pool_flush_out;
+int rsk_pool_flush(rsk_ctx *ctx, const rsk_pool *pool, uint64_t now_ms, const rsk_pool_flush_out *out, void *stream);
+int rsk_pool_flush_host(const rsk_pool *pool, uint64_t now_ms, const rsk_pool_flush_out *out, int nthreads);
+
 /* ---- conv table: a DATA packet's conv, the convs' activity counts and their flush ------------------ */
 /* The reference's last lookup before a payload reaches anybody: on a server SubGroup::OnRecv looks
  * BuildConvKey(info->dst, head->Conv()) up in the SubGroup of the packet's IdBuf (server/SubGroup.cpp:31-50,

@@ -56,6 +56,8 @@ CONV_BY_DST, CONV_BY_ID = 0x1, 0x2
 CONV_CLOSE_HOLD = 0x1
 CONN_CLOSE_REMOVE, CONN_CLOSE_SWEEP = 0x1, 0x2
 CONN_CREATE_LIST, CONN_CREATE_REPEAT = 0x1, 0x2
+POOL_LIVE = 0x1
+POOL_TOUCH = 0x1
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.c_void_p  # all arrays passed as raw addresses
@@ -284,6 +286,41 @@ class ConvFlushOut(ctypes.Structure):
     _fields_ = [("dead_rows", _vp), ("n_dead", _vp), ("n_alive", _vp)]
 
 
+class Pool(ctypes.Structure):
+    _fields_ = [("state", _vp), ("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("seq", _vp), ("ack", _vp),
+                ("expiry", _vp), ("index", _vp), ("capacity", ctypes.c_uint32)]
+
+
+class PoolAddIn(ctypes.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("seq", _vp), ("ack", _vp), ("parse_status", _vp),
+                ("expiry", ctypes.c_uint64), ("u_max", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("work", _vp)]
+
+
+class PoolAddOut(ctypes.Structure):
+    _fields_ = [("row", _vp), ("new_rows", _vp), ("new_first", _vp), ("n_new", _vp), ("n_again", _vp), ("n_full", _vp),
+                ("n_zero_port", _vp)]
+
+
+class PoolOffersOut(ctypes.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("sp", _vp), ("dp", _vp), ("ack", _vp), ("flag", _vp), ("conn_key", _vp),
+                ("n_offer", _vp), ("offer_ack_row", _vp), ("offer_sock_row", _vp), ("n_over", _vp),
+                ("m_max", ctypes.c_uint32)]
+
+
+class PoolSettleIn(ctypes.Structure):
+    _fields_ = [("new_offer", _vp), ("n_new", _vp), ("offer_ack_row", _vp), ("offer_sock_row", _vp),
+                ("new_max", ctypes.c_uint32), ("m_max", ctypes.c_uint32), ("miss", _vp), ("src", _vp), ("dst", _vp),
+                ("sp", _vp), ("dp", _vp), ("work", _vp)]
+
+
+class PoolSettleOut(ctypes.Structure):
+    _fields_ = [("taken_sock_rows", _vp), ("closed_sock_rows", _vp), ("n_closed", _vp), ("n_purged_ack", _vp)]
+
+
+class PoolFlushOut(ctypes.Structure):
+    _fields_ = [("dead_rows", _vp), ("n_dead", _vp)]
+
+
 class PortList(ctypes.Structure):
     _fields_ = [("n_single", ctypes.c_uint16), ("n_range", ctypes.c_uint16),
                 ("single", ctypes.c_uint16 * FILTER_MAX_PORTS), ("range", (ctypes.c_uint16 * 2) * FILTER_MAX_PORTS)]
@@ -424,6 +461,25 @@ SIGNATURES = [
     ("rsk_conv_send_host", ctypes.c_int,
      [ctypes.POINTER(ConvTable), ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ConvSendOut), ctypes.c_int]),
     ("rsk_conv_flush_host", ctypes.c_int, [ctypes.POINTER(ConvTable), ctypes.POINTER(ConvFlushOut), ctypes.c_int]),
+    ("rsk_pool_index_build", ctypes.c_int, [_vp, ctypes.POINTER(Pool), _vp, _vp]),
+    ("rsk_pool_index_build_host", ctypes.c_int, [ctypes.POINTER(Pool), _vp, ctypes.c_int]),
+    ("rsk_pool_add_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_pool_add_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(Pool), ctypes.c_uint32, ctypes.POINTER(PoolAddIn), ctypes.POINTER(PoolAddOut), _vp]),
+    ("rsk_pool_add_host", ctypes.c_int,
+     [ctypes.POINTER(Pool), ctypes.c_uint32, ctypes.POINTER(PoolAddIn), ctypes.POINTER(PoolAddOut), ctypes.c_int]),
+    ("rsk_pool_offers", ctypes.c_int, [_vp, ctypes.POINTER(Pool), ctypes.POINTER(Pool), ctypes.POINTER(PoolOffersOut), _vp]),
+    ("rsk_pool_offers_host", ctypes.c_int,
+     [ctypes.POINTER(Pool), ctypes.POINTER(Pool), ctypes.POINTER(PoolOffersOut), ctypes.c_int]),
+    ("rsk_pool_settle_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("rsk_pool_settle_batch", ctypes.c_int,
+     [_vp, ctypes.POINTER(Pool), ctypes.POINTER(Pool), ctypes.c_uint32, ctypes.POINTER(PoolSettleIn),
+      ctypes.POINTER(PoolSettleOut), _vp]),
+    ("rsk_pool_settle_host", ctypes.c_int,
+     [ctypes.POINTER(Pool), ctypes.POINTER(Pool), ctypes.c_uint32, ctypes.POINTER(PoolSettleIn),
+      ctypes.POINTER(PoolSettleOut), ctypes.c_int]),
+    ("rsk_pool_flush", ctypes.c_int, [_vp, ctypes.POINTER(Pool), ctypes.c_uint64, ctypes.POINTER(PoolFlushOut), _vp]),
+    ("rsk_pool_flush_host", ctypes.c_int, [ctypes.POINTER(Pool), ctypes.c_uint64, ctypes.POINTER(PoolFlushOut), ctypes.c_int]),
     ("rsk_compute_hash", _vp, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_hash_equal", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
     ("rsk_enchead_enc2buf", _vp,

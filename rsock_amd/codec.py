@@ -829,6 +829,156 @@ def conv_flush_host(tab: ConvTable, dead_rows=None, n_dead=None, n_alive=None, n
         raise RskError(f"rsk_conv_flush_host failed: rc={rc}")
 
 
+_POOL_COLUMNS = (("state", torch.uint8), ("src", torch.int32), ("dst", torch.int32), ("sp", torch.int16),
+                 ("dp", torch.int16), ("seq", torch.int32), ("ack", torch.int32), ("expiry", torch.int64))
+
+
+@dataclass
+class PoolTable:
+    """A tuple pool (rsk_pool): TcpAckPool's records (vals=True: with seq / ack) or the accepted sockets nobody
+    has asked for yet (vals=False), in columns of torch tensors (signed storage of the unsigned C types) plus the
+    opaque index.  Shaped like ConnTable: on a device the pool calls of Codec take it, on "cpu" the pool_*_host
+    twins below; after any host edit of state or a tuple column call rebuild()."""
+
+    capacity: int
+    state: torch.Tensor          # uint8: POOL_LIVE
+    src: torch.Tensor
+    dst: torch.Tensor
+    sp: torch.Tensor
+    dp: torch.Tensor
+    seq: torch.Tensor | None
+    ack: torch.Tensor | None
+    expiry: torch.Tensor         # int64 storage of u64
+    index: torch.Tensor          # opaque, rsk_conn_index_bytes(capacity, CONN_BY_ID) bytes
+
+    @classmethod
+    def alloc(cls, capacity: int, device, vals: bool = True) -> "PoolTable":
+        nbytes = lib().rsk_conn_index_bytes(capacity, _abi.CONN_BY_ID)
+        if nbytes == 0:
+            raise RskError(f"rsk_conn_index_bytes: bad capacity {capacity}")
+        cols = {name: torch.zeros(capacity, dtype=dt, device=device) for name, dt in _POOL_COLUMNS}
+        if not vals:
+            cols["seq"] = cols["ack"] = None
+        return cls(capacity=int(capacity), index=torch.full((nbytes // 4,), -1, dtype=torch.int32, device=device), **cols)
+
+    def abi(self) -> _abi.Pool:
+        return _abi.Pool(*[_ptr(getattr(self, name)) for name, _ in _POOL_COLUMNS], _ptr(self.index), self.capacity)
+
+    def load(self, **cols) -> "PoolTable":
+        """Copy numpy arrays (any integer dtype of the column's width) into the named columns."""
+        for name, a in cols.items():
+            t = getattr(self, name)
+            a = np.ascontiguousarray(a)
+            t.copy_(torch.from_numpy(a.view(f"i{a.dtype.itemsize}" if t.dtype != torch.uint8 else np.uint8)))
+        return self
+
+    def to(self, device) -> "PoolTable":
+        """A copy of every column and of the index on `device` (the index is valid on either side)."""
+        mv = lambda t: None if t is None else t.to(device, copy=True)  # noqa: E731
+        return PoolTable(self.capacity, *[mv(getattr(self, name)) for name, _ in _POOL_COLUMNS], mv(self.index))
+
+    def column(self, name: str) -> np.ndarray:
+        """A column (or the index) on the host as its unsigned C type."""
+        a = getattr(self, name).cpu().numpy()
+        return a.view(f"u{a.dtype.itemsize}")
+
+    def add_work(self, u_max: int) -> torch.Tensor:
+        """The work buffer of pool_add_batch / pool_add_host for at most u_max rows per call (rsk_pool_add_bytes),
+        on the pool's device; one per stream that runs the call."""
+        nbytes = lib().rsk_pool_add_bytes(u_max, self.capacity)
+        if nbytes == 0:
+            raise RskError(f"rsk_pool_add_bytes: bad u_max {u_max}")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
+    def settle_work(self, sock: "PoolTable") -> torch.Tensor:
+        """The work buffer of pool_settle_batch / pool_settle_host for this ack pool and the socket pool `sock`
+        (rsk_pool_settle_bytes), on the pool's device; one per stream that runs the call."""
+        nbytes = lib().rsk_pool_settle_bytes(self.capacity, sock.capacity)
+        if nbytes == 0:
+            raise RskError("rsk_pool_settle_bytes: bad capacity")
+        return torch.empty(nbytes // 4, dtype=torch.int32, device=self.index.device)
+
+    def rebuild(self, codec: "Codec | None" = None, stream=None, n_dup: torch.Tensor | None = None) -> None:
+        """rsk_pool_index_build on `stream` (a device pool, with its Codec), or the host twin (a "cpu" pool,
+        codec None).  n_dup [1] receives the LIVE rows that lost their tuple to a lower row."""
+        if (codec is None) != (self.index.device.type == "cpu"):
+            raise RskError("PoolTable.rebuild: a device pool takes its Codec, a cpu pool none")
+        if codec is None:
+            _check(lib().rsk_pool_index_build_host(ctypes.byref(self.abi()), _ptr(n_dup), 1), "rsk_pool_index_build_host")
+        else:
+            _check(lib().rsk_pool_index_build(codec._ctx, ctypes.byref(self.abi()), _ptr(n_dup), _stream(stream)),
+                   "rsk_pool_index_build")
+
+
+def _pool_add_structs(src, dst, sp, dp, expiry, u_max, work, seq, ack, parse_status, touch, row, new_rows, new_first,
+                      n_new, n_again, n_full, n_zero_port):
+    cin = _abi.PoolAddIn(_addr(src), _addr(dst), _addr(sp), _addr(dp), _addr(seq), _addr(ack), _addr(parse_status),
+                         int(expiry) & 0xFFFFFFFFFFFFFFFF, int(u_max), _abi.POOL_TOUCH if touch else 0, _addr(work))
+    cout = _abi.PoolAddOut(_addr(row), _addr(new_rows), _addr(new_first), _addr(n_new), _addr(n_again), _addr(n_full),
+                           _addr(n_zero_port))
+    return cin, cout
+
+
+def _pool_offers_struct(offers: ConnOffers, offer_ack_row, offer_sock_row, n_over):
+    m = len(offers.src) if offers.m_max is None else int(offers.m_max)
+    return _abi.PoolOffersOut(_addr(offers.src), _addr(offers.dst), _addr(offers.sp), _addr(offers.dp), _addr(offers.ack),
+                              _addr(offers.flag), _addr(offers.conn_key), _addr(offers.n_offer), _addr(offer_ack_row),
+                              _addr(offer_sock_row), _addr(n_over), m)
+
+
+def _pool_settle_structs(new_offer, n_new, offer_ack_row, offer_sock_row, m_max, miss, src, dst, sp, dp, work, new_max,
+                         taken_sock_rows, closed_sock_rows, n_closed, n_purged_ack):
+    if new_max is None:
+        new_max = 0 if new_offer is None else len(new_offer)
+    if m_max is None:
+        m_max = max(1, 0 if offer_ack_row is None else len(offer_ack_row))
+    cin = _abi.PoolSettleIn(_addr(new_offer), _addr(n_new), _addr(offer_ack_row), _addr(offer_sock_row), int(new_max),
+                            int(m_max), _addr(miss), _addr(src), _addr(dst), _addr(sp), _addr(dp), _addr(work))
+    cout = _abi.PoolSettleOut(_addr(taken_sock_rows), _addr(closed_sock_rows), _addr(n_closed), _addr(n_purged_ack))
+    return (0 if miss is None else len(miss)), cin, cout
+
+
+def pool_add_host(pool: PoolTable, src, dst, sp, dp, expiry: int, u_max: int, work, seq=None, ack=None,
+                  parse_status=None, touch: bool = False, row=None, new_rows=None, new_first=None, n_new=None,
+                  n_again=None, n_full=None, n_zero_port=None, nthreads: int = 1) -> None:
+    """rsk_pool_add_host on a "cpu" PoolTable (no GPU); the arguments of Codec.pool_add_batch."""
+    cin, cout = _pool_add_structs(src, dst, sp, dp, expiry, u_max, work, seq, ack, parse_status, touch, row, new_rows,
+                                  new_first, n_new, n_again, n_full, n_zero_port)
+    rc = lib().rsk_pool_add_host(ctypes.byref(pool.abi()), len(src), ctypes.byref(cin), ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_pool_add_host failed: rc={rc}")
+
+
+def pool_offers_host(ack_pool: PoolTable, sock_pool: PoolTable, offers: ConnOffers, offer_ack_row=None,
+                     offer_sock_row=None, n_over=None, nthreads: int = 1) -> None:
+    """rsk_pool_offers_host on "cpu" PoolTables (no GPU); the arguments of Codec.pool_offers."""
+    out = _pool_offers_struct(offers, offer_ack_row, offer_sock_row, n_over)
+    rc = lib().rsk_pool_offers_host(ctypes.byref(ack_pool.abi()), ctypes.byref(sock_pool.abi()), ctypes.byref(out), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_pool_offers_host failed: rc={rc}")
+
+
+def pool_settle_host(ack_pool: PoolTable, sock_pool: PoolTable, work, new_offer=None, n_new=None, offer_ack_row=None,
+                     offer_sock_row=None, m_max: int | None = None, miss=None, src=None, dst=None, sp=None, dp=None,
+                     new_max: int | None = None, taken_sock_rows=None, closed_sock_rows=None, n_closed=None,
+                     n_purged_ack=None, nthreads: int = 1) -> None:
+    """rsk_pool_settle_host on "cpu" PoolTables (no GPU); the arguments of Codec.pool_settle_batch."""
+    n, cin, cout = _pool_settle_structs(new_offer, n_new, offer_ack_row, offer_sock_row, m_max, miss, src, dst, sp, dp,
+                                        work, new_max, taken_sock_rows, closed_sock_rows, n_closed, n_purged_ack)
+    rc = lib().rsk_pool_settle_host(ctypes.byref(ack_pool.abi()), ctypes.byref(sock_pool.abi()), n, ctypes.byref(cin),
+                                    ctypes.byref(cout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_pool_settle_host failed: rc={rc}")
+
+
+def pool_flush_host(pool: PoolTable, now_ms: int, dead_rows=None, n_dead=None, nthreads: int = 1) -> None:
+    """rsk_pool_flush_host on a "cpu" PoolTable (no GPU); the arguments of Codec.pool_flush."""
+    fout = _abi.PoolFlushOut(_addr(dead_rows), _addr(n_dead))
+    rc = lib().rsk_pool_flush_host(ctypes.byref(pool.abi()), int(now_ms) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(fout), nthreads)
+    if rc != 0:
+        raise RskError(f"rsk_pool_flush_host failed: rc={rc}")
+
+
 @dataclass
 class TcpInfoBuffers:
     """SoA TcpInfo outputs of RawTcp::RawInput for n captured packets (rsk_tcpinfo_out)."""
@@ -1318,6 +1468,44 @@ class Codec:
         fout = _abi.ConvFlushOut(_ptr(dead_rows), _ptr(n_dead), _ptr(n_alive))
         _check(lib().rsk_conv_flush(self._ctx, ctypes.byref(tab.abi()), ctypes.byref(fout), _stream(stream)),
                "rsk_conv_flush")
+
+    def pool_add_batch(self, pool: "PoolTable", src, dst, sp, dp, expiry: int, u_max: int, work, seq=None, ack=None,
+                       parse_status=None, touch: bool = False, row=None, new_rows=None, new_first=None, n_new=None,
+                       n_again=None, n_full=None, n_zero_port=None, stream=None) -> None:
+        """TcpAckPool::AddInfoFromPeer / ServerNetManager::add2Pool on the device pool (rsk_pool_add_batch): the
+        rows with parse_status == PARSE_SYN (every row without parse_status) and both ports, the first u_max of
+        them; a tuple in the pool keeps its row (touch: its expiry moves), the new ones take the vacant rows in
+        first-arrival order.  work: pool.add_work(u_max)."""
+        cin, cout = _pool_add_structs(src, dst, sp, dp, expiry, u_max, work, seq, ack, parse_status, touch, row,
+                                      new_rows, new_first, n_new, n_again, n_full, n_zero_port)
+        _check(lib().rsk_pool_add_batch(self._ctx, ctypes.byref(pool.abi()), len(src), ctypes.byref(cin),
+                                        ctypes.byref(cout), _stream(stream)), "rsk_pool_add_batch")
+
+    def pool_offers(self, ack_pool: "PoolTable", sock_pool: "PoolTable", offers: "ConnOffers", offer_ack_row=None,
+                    offer_sock_row=None, n_over=None, stream=None) -> None:
+        """The join of the two pools into conn_create_batch's offers (rsk_pool_offers): one offer per record whose
+        tuple has a socket, in row order; offers.conn_key, when given, receives key_for_tcp(sp, dp)."""
+        out = _pool_offers_struct(offers, offer_ack_row, offer_sock_row, n_over)
+        _check(lib().rsk_pool_offers(self._ctx, ctypes.byref(ack_pool.abi()), ctypes.byref(sock_pool.abi()),
+                                     ctypes.byref(out), _stream(stream)), "rsk_pool_offers")
+
+    def pool_settle_batch(self, ack_pool: "PoolTable", sock_pool: "PoolTable", work, new_offer=None, n_new=None,
+                          offer_ack_row=None, offer_sock_row=None, m_max: int | None = None, miss=None, src=None,
+                          dst=None, sp=None, dp=None, new_max: int | None = None, taken_sock_rows=None,
+                          closed_sock_rows=None, n_closed=None, n_purged_ack=None, stream=None) -> None:
+        """The pools behind a batch (rsk_pool_settle_batch): the rows of the offers that became conns leave, and so
+        does what a still-missing packet's tuple has in one pool only.  work: ack_pool.settle_work(sock_pool)."""
+        n, cin, cout = _pool_settle_structs(new_offer, n_new, offer_ack_row, offer_sock_row, m_max, miss, src, dst, sp,
+                                            dp, work, new_max, taken_sock_rows, closed_sock_rows, n_closed, n_purged_ack)
+        _check(lib().rsk_pool_settle_batch(self._ctx, ctypes.byref(ack_pool.abi()), ctypes.byref(sock_pool.abi()), n,
+                                           ctypes.byref(cin), ctypes.byref(cout), _stream(stream)), "rsk_pool_settle_batch")
+
+    def pool_flush(self, pool: "PoolTable", now_ms: int, dead_rows=None, n_dead=None, stream=None) -> None:
+        """TcpAckPool::OnFlush / ServerNetManager::OnFlush (rsk_pool_flush): the LIVE rows with expiry <= now_ms
+        leave; dead_rows [capacity] lists them in row order, n_dead [1] counts them."""
+        fout = _abi.PoolFlushOut(_ptr(dead_rows), _ptr(n_dead))
+        _check(lib().rsk_pool_flush(self._ctx, ctypes.byref(pool.abi()), int(now_ms) & 0xFFFFFFFFFFFFFFFF,
+                                    ctypes.byref(fout), _stream(stream)), "rsk_pool_flush")
 
     # ---- reference single-call signatures (GPU round trip each) -----------------------------
     def compute_hash(self, data: bytes) -> bytes | None:

@@ -30,7 +30,7 @@ inline size_t deliver_ws_bytes(uint32_t n) { return ((size_t)(n + kDeliverTile -
 // so a reserve for any batch size covers the flush.  rsk_conn_close_batch keeps two such arrays over the row tiles
 // (the rows that lose ALIVE / LIVE, and the pick candidates that stay), each with its total.
 constexpr uint32_t kControlTile = 2048, kFlushTile = 1024;
-inline size_t control_ws_bytes(uint32_t n) {
+constexpr size_t control_ws_bytes(uint32_t n) {
     const size_t tiles = ((size_t)n + kControlTile - 1u) / kControlTile, rows = 2u * (RSK_CONN_MAX_ROWS / kFlushTile) + 1u;
     return ((tiles > rows ? tiles : rows) + 1u) * 8u;
 }

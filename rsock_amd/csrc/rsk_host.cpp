@@ -3,7 +3,7 @@
 // payloads, each over contiguous shards on std::threads; and the host twins of the payload delivery
 // (rsk_deliver_host), of the checksum verification (rsk_verify_wire_host) and of the connection table
 // (rsk_conn_*_host) with its send pick (rsk_conn_pick_*host), its control packets and keepalive timer (rsk_control_host,
-// rsk_keepalive_flush_host), its close (rsk_conn_close_host) and of the conv table (rsk_conv_*_host); the single-frame slot staging, the capture filter's text form and the connection
+// rsk_keepalive_flush_host), its close (rsk_conn_close_host), of the conv table (rsk_conv_*_host) and of the tuple pool (rsk_pool_*_host); the single-frame slot staging, the capture filter's text form and the connection
 // keys.  Pure host code (no HIP calls).
 #include <atomic>
 #include <cstring>
@@ -17,6 +17,7 @@
 #include "rsk_conn_create.h"
 #include "rsk_conv_create.h"
 #include "rsk_pick.h"
+#include "rsk_pool.h"
 
 namespace {
 
@@ -1180,6 +1181,185 @@ extern "C" int rsk_conv_close_host(const rsk_conv_table *t, const rsk_conv_rows 
     if (out->n_reopened) *out->n_reopened = n_re;
     if (out->n_rst_again) *out->n_rst_again = n_again;
     if (out->n_unknown) *out->n_unknown += n_re;
+    return RSK_OK;
+}
+
+// ---- tuple pool ---------------------------------------------------------------------------------------------
+namespace {
+
+struct HostPool {
+    const rsk_pool *p;
+    uint32_t entry(uint32_t s) const { return p->index[s]; }
+    uint64_t key(uint32_t row) const { return rsk::tuple_key(p->src[row], p->dst[row]); }
+    uint64_t id(uint32_t row) const { return rsk::tuple_ports(p->sp[row], p->dp[row]); }
+};
+
+// The LIVE row of a tuple, or RSK_CONN_NONE.  An index that was never built may name a row that is not LIVE.
+uint32_t pool_find(const rsk_pool *p, uint64_t key, uint64_t ports) {
+    const uint32_t r = rsk::conn_lookup(HostPool{p}, p->capacity, true, key, ports);
+    return r < p->capacity && (p->state[r] & RSK_POOL_LIVE) ? r : RSK_CONN_NONE;
+}
+
+// The marked rows (settle) or the expired ones (flush, mark == nullptr) leave in row order; the listed ones (the
+// settle's purged rows, every row of the flush) go to list.  The index is rebuilt only when a row left.
+void pool_leave(const rsk_pool *p, const uint8_t *mark, uint64_t now, uint32_t *list, uint32_t *n_listed) {
+    uint32_t left = 0, nl = 0;
+    for (uint32_t r = 0; r < p->capacity; ++r) {
+        if (!(p->state[r] & RSK_POOL_LIVE)) continue;
+        if (mark ? mark[r] == rsk::kPoolStays : p->expiry[r] > now) continue;
+        if (!mark || mark[r] == rsk::kPoolPurged) {
+            if (list) list[nl] = r;
+            ++nl;
+        }
+        p->state[r] = (uint8_t)(p->state[r] & ~RSK_POOL_LIVE);
+        ++left;
+    }
+    if (left) index_build_host(HostPool{p}, p->index, p->state, p->capacity, true, nullptr);
+    if (n_listed) *n_listed = nl;
+}
+
+}  // namespace
+
+extern "C" int rsk_pool_index_build_host(const rsk_pool *p, uint32_t *n_dup, int /*nthreads*/) {
+    if (!rsk::pool_ok(p, false)) return RSK_EINVAL;
+    index_build_host(HostPool{p}, p->index, p->state, p->capacity, true, n_dup);
+    return RSK_OK;
+}
+
+extern "C" uint64_t rsk_pool_add_bytes(uint32_t u_max, uint32_t capacity) { return rsk_conv_create_bytes(u_max, capacity); }
+
+extern "C" uint64_t rsk_pool_settle_bytes(uint32_t cap_ack, uint32_t cap_sock) {
+    if (!rsk::pool_cap_ok(cap_ack) || !rsk::pool_cap_ok(cap_sock)) return 0;
+    return rsk::pool_settle_bytes(cap_ack, cap_sock);
+}
+
+// One walk over the considered rows in input order: a tuple the pool holds is touched, a new one takes the next
+// vacant row and goes into the index at once, so its later arrivals find it there.
+extern "C" int rsk_pool_add_host(const rsk_pool *p, uint32_t n, const rsk_pool_add_in *in, const rsk_pool_add_out *out,
+                                 int /*nthreads*/) {
+    if (!rsk::pool_add_args_ok(p, n, in, out)) return RSK_EINVAL;
+    const uint32_t cap = p->capacity, slots = rsk::conn_slots(cap);
+    const bool touch = (in->flags & RSK_POOL_TOUCH) != 0;
+    const HostPool h{p};
+    auto considered = [&](uint32_t i) { return !in->parse_status || in->parse_status[i] == RSK_PARSE_SYN; };
+    auto ports_ok = [&](uint32_t i) { return in->sp[i] != 0 && in->dp[i] != 0; };
+    uint32_t n_new = 0, n_again = 0, n_zero = 0, taken = 0, v = 0;
+    std::map<std::pair<uint64_t, uint64_t>, int> refused;  // the tuples a full pool left without a row
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!considered(i)) continue;
+        if (!ports_ok(i)) { ++n_zero; continue; }
+        if (taken == in->u_max) continue;
+        ++taken;
+        const uint64_t key = rsk::tuple_key(in->src[i], in->dst[i]), ports = rsk::tuple_ports(in->sp[i], in->dp[i]);
+        const uint32_t r = pool_find(p, key, ports);
+        if (r != RSK_CONN_NONE) {
+            ++n_again;
+            if (touch) p->expiry[r] = in->expiry;
+            continue;
+        }
+        while (v < cap && (p->state[v] & RSK_POOL_LIVE)) ++v;
+        if (v == cap) {
+            if (!refused.emplace(std::make_pair(key, ports), 0).second) ++n_again;
+            continue;
+        }
+        p->src[v] = in->src[i];
+        p->dst[v] = in->dst[i];
+        p->sp[v] = in->sp[i];
+        p->dp[v] = in->dp[i];
+        if (p->seq) p->seq[v] = in->seq[i];
+        if (p->ack) p->ack[v] = in->ack[i];
+        p->expiry[v] = in->expiry;
+        p->state[v] = RSK_POOL_LIVE;
+        // rsk_pool_index_build's rule: a free entry, or the lowest row of the tuple; an entry that is no row (an
+        // index that was never built) ends the walk, as it ends a lookup
+        uint32_t s = rsk::conn_home(key, ports, slots);
+        for (uint32_t step = 0; step < slots; ++step, s = rsk::conn_next(s, slots)) {
+            const uint32_t e = p->index[s];
+            if (e == rsk::kConnEmpty) { p->index[s] = v; break; }
+            if (e >= cap) break;
+            if (h.key(e) == key && h.id(e) == ports) {
+                if (v < e) p->index[s] = v;
+                break;
+            }
+        }
+        if (out->new_rows) out->new_rows[n_new] = v;
+        if (out->new_first) out->new_first[n_new] = i;
+        ++n_new;
+        ++v;
+    }
+    for (uint32_t i = 0; out->row && i < n; ++i)
+        out->row[i] = considered(i) && ports_ok(i)
+                          ? pool_find(p, rsk::tuple_key(in->src[i], in->dst[i]), rsk::tuple_ports(in->sp[i], in->dp[i]))
+                          : RSK_CONN_NONE;
+    if (out->n_new) *out->n_new = n_new;
+    if (out->n_again) *out->n_again = n_again;
+    if (out->n_full) *out->n_full = (uint32_t)refused.size();
+    if (out->n_zero_port) *out->n_zero_port = n_zero;
+    return RSK_OK;
+}
+
+extern "C" int rsk_pool_offers_host(const rsk_pool *pa, const rsk_pool *ps, const rsk_pool_offers_out *out, int /*nthreads*/) {
+    if (!rsk::pool_offers_args_ok(pa, ps, out)) return RSK_EINVAL;
+    const HostPool h{pa};
+    uint32_t total = 0;
+    for (uint32_t r = 0; r < pa->capacity; ++r) {
+        if (!(pa->state[r] & RSK_POOL_LIVE)) continue;
+        const uint32_t sr = pool_find(ps, h.key(r), h.id(r));
+        if (sr == RSK_CONN_NONE) continue;
+        const uint32_t o = total++;
+        if (o >= out->m_max) continue;
+        out->src[o] = pa->src[r];
+        out->dst[o] = pa->dst[r];
+        out->sp[o] = pa->sp[r];
+        out->dp[o] = pa->dp[r];
+        out->ack[o] = pa->ack[r];   // the record's ack, never its seq
+        out->flag[o] = RSK_TH_ACK;  // the flag the conn sends with, never the handshake's
+        if (out->conn_key) out->conn_key[o] = rsk_key_for_tcp(pa->sp[r], pa->dp[r]);
+        if (out->offer_ack_row) out->offer_ack_row[o] = r;
+        if (out->offer_sock_row) out->offer_sock_row[o] = sr;
+    }
+    const uint32_t no = total < out->m_max ? total : out->m_max;
+    *out->n_offer = no;
+    if (out->n_over) *out->n_over = total - no;
+    return RSK_OK;
+}
+
+extern "C" int rsk_pool_settle_host(const rsk_pool *pa, const rsk_pool *ps, uint32_t n, const rsk_pool_settle_in *in,
+                                    const rsk_pool_settle_out *out, int /*nthreads*/) {
+    if (!rsk::pool_settle_args_ok(pa, ps, n, in, out)) return RSK_EINVAL;
+    uint8_t *mark_a = static_cast<uint8_t *>(in->work), *mark_s = mark_a + rsk::pool_round16(pa->capacity);
+    std::memset(mark_a, 0, (size_t)rsk::pool_settle_bytes(pa->capacity, ps->capacity));
+    const uint32_t m = in->new_max ? (*in->n_new < in->new_max ? *in->n_new : in->new_max) : 0u;
+    for (uint32_t j = 0; j < m; ++j) {  // (a)
+        const uint32_t o = in->new_offer[j];
+        uint32_t sr = RSK_CONN_NONE;
+        if (o < in->m_max) {
+            const uint32_t ar = in->offer_ack_row[o];
+            sr = in->offer_sock_row[o];
+            if (ar < pa->capacity) mark_a[ar] = rsk::kPoolTaken;
+            if (sr < ps->capacity) mark_s[sr] = rsk::kPoolTaken;
+            else sr = RSK_CONN_NONE;
+        }
+        if (out->taken_sock_rows) out->taken_sock_rows[j] = sr;
+    }
+    for (uint32_t i = 0; i < n; ++i) {  // (b)
+        if (in->miss[i] != RSK_RECV_VALID) continue;
+        const uint64_t key = rsk::tuple_key(in->src[i], in->dst[i]), ports = rsk::tuple_ports(in->sp[i], in->dp[i]);
+        const uint32_t ra = pool_find(pa, key, ports), rs = pool_find(ps, key, ports);
+        const bool in_a = ra != RSK_CONN_NONE && mark_a[ra] != rsk::kPoolTaken;
+        const bool in_s = rs != RSK_CONN_NONE && mark_s[rs] != rsk::kPoolTaken;
+        if (in_a == in_s) continue;
+        if (in_a) mark_a[ra] = rsk::kPoolPurged;
+        else mark_s[rs] = rsk::kPoolPurged;
+    }
+    pool_leave(pa, mark_a, 0, nullptr, out->n_purged_ack);
+    pool_leave(ps, mark_s, 0, out->closed_sock_rows, out->n_closed);
+    return RSK_OK;
+}
+
+extern "C" int rsk_pool_flush_host(const rsk_pool *p, uint64_t now_ms, const rsk_pool_flush_out *out, int /*nthreads*/) {
+    if (!rsk::pool_flush_args_ok(p, out)) return RSK_EINVAL;
+    pool_leave(p, nullptr, now_ms, out->dead_rows, out->n_dead);
     return RSK_OK;
 }
 
