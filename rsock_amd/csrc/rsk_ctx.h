@@ -25,10 +25,17 @@ enum WsKind { WS_COMPACT = 0, WS_SEQ = 1, WS_DEMUX = 2, WS_ENC = 3, WS_DELIVER =
 // WS_DELIVER (rsk_deliver.hip): one 64-bit sum per tile of kDeliverTile positions, and the total
 constexpr uint32_t kDeliverTile = 1024;
 inline size_t deliver_ws_bytes(uint32_t n) { return ((size_t)(n + kDeliverTile - 1u) / kDeliverTile + 1u) * 8u; }
-// WS_CONTROL (rsk_control.hip, rsk_conv.hip, rsk_conv_create.hip, rsk_conv_close.hip, rsk_conn_close.hip): two 32-bit counts per tile of kControlTile packets
-// (rsk_control_batch, rsk_conv_resolve_batch, rsk_conv_create_batch: its packet tiles, then its row tiles) or kFlushTile rows (rsk_keepalive_flush, rsk_conv_flush, rsk_conv_close_batch), and the totals; never less than the largest table's flush needs,
+// WS_CONTROL (rsk_control.hip, rsk_conv.hip, rsk_conv_create.hip, rsk_conv_close.hip, rsk_conn_close.hip, rsk_conn_create.hip,
+// rsk_pool.hip): two 32-bit counts per tile of kControlTile packets
+// (rsk_control_batch, rsk_conv_resolve_batch, rsk_conv_create_batch: its packet tiles, then its row tiles;
+// rsk_conn_create_batch: its packet tiles, then the tiles of its considered items or offers and of the rows;
+// rsk_pool_add_batch: its packet tiles, then the tiles of its considered rows and of the pool's rows) or kFlushTile rows
+// (rsk_keepalive_flush, rsk_conv_flush, rsk_conv_close_batch, rsk_pool_offers, rsk_pool_flush; rsk_pool_settle_batch:
+// the row tiles of both pools), and the totals; never less than the largest table's flush needs,
 // so a reserve for any batch size covers the flush.  rsk_conn_close_batch keeps two such arrays over the row tiles
 // (the rows that lose ALIVE / LIVE, and the pick candidates that stay), each with its total.
+// Every entry point lays the scratch out for itself and reads nothing an earlier call left in it: the calls of one
+// stream run in order, and tests/test_gpu_session.py runs them all, batch after batch, on one stream's scratch.
 constexpr uint32_t kControlTile = 2048, kFlushTile = 1024;
 constexpr size_t control_ws_bytes(uint32_t n) {
     const size_t tiles = ((size_t)n + kControlTile - 1u) / kControlTile, rows = 2u * (RSK_CONN_MAX_ROWS / kFlushTile) + 1u;
